@@ -21,7 +21,15 @@ duration from HIP events recorded on the launch stream inside the timed region. 
 ``cpu_baseline`` is the reference's CPU op sequence (oracle/ref_torch_cpu.py) on a bounded
 sample of the same workload, rank 0, N=1 only.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps (the dominant kernel's HIP events are recorded
+inside them) and prints the line. Everything that takes work of its own — the CPU baseline, the
+HBM probes, the sampled result check against the host fp64 chain, the same-N one-GPU anchor of
+an N > 1 line, and the untimed diagnostic rounds after the timed ones (partial-only rounds, the
+event-timed exchange tail, the dynamic wave's tile timing, one burst's fold) — runs only with
+``--full``; without it those keys of the line are null. ``--dump-outputs DIR`` writes the result
+of the last timed step as ``DIR/<tensor name>.npy`` (see dump_outputs).
 
 Launch. ``--gpus N > 1`` without ``WORLD_SIZE`` in the environment makes this process a
 launcher that never touches the GPU: it starts N fresh rank processes of this script (RANK /
@@ -458,6 +466,47 @@ def flat_index(layout: ModelLayout, picks: list[tuple[int, int]], elem_bytes: in
     return torch.tensor([offs[s] + i for s, i in picks], dtype=torch.int64, device=device)
 
 
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: the most one run writes
+
+
+def dump_outputs(out_dir: str, named: list[tuple[str, torch.Tensor]], seed: int = 20240607) -> dict:
+    """--dump-outputs: write the result tensors of the last timed step as ``out_dir/<name>.npy``
+    (float64 results as float64, every other dtype as float32). Results of at most
+    DUMP_BUDGET_BYTES in all are written whole, in their own shapes. A larger result is sampled:
+    of every tensor the same fraction of elements (at least one), at flat positions drawn with a
+    generator seeded by ``seed`` and the tensor's place in ``named``, sorted — the same positions
+    in every run of the same arguments, so two builds compare element for element."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    width = [8 if t.dtype == torch.float64 else 4 for _, t in named]
+    total = sum(t.numel() * w for (_, t), w in zip(named, width))
+    budget = DUMP_BUDGET_BYTES - 256 * len(named)  # the .npy headers count too
+    frac = min(1.0, budget / max(total, 1))
+    # the one-element floor of a sampled tensor comes out of the others' share
+    if frac < 1.0:
+        frac *= max(0.0, 1.0 - 8 * len(named) / budget)
+    written = 0
+    for i, ((name, t), w) in enumerate(zip(named, width)):
+        flat = t.detach().reshape(-1)
+        if frac < 1.0:
+            k = max(1, int(flat.numel() * frac))
+            idx = np.sort(np.random.default_rng([seed, i]).integers(0, flat.numel(), size=k))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float64 if w == 8 else torch.float32).cpu().numpy()
+        if frac >= 1.0:
+            a = a.reshape(tuple(t.shape))
+        np.save(d / (name.replace("/", "_") + ".npy"), a)
+        written += a.nbytes
+    assert written <= budget, written
+    return {"dir": str(d), "arrays": len(named), "bytes": written, "sampled": frac < 1.0}
+
+
+def layout_views(layout: ModelLayout, flat: torch.Tensor, elem_bytes: int) -> list[tuple[str, torch.Tensor]]:
+    """(name, tensor) of every layout tensor inside a padded flat buffer (ModelLayout.padded_offsets)."""
+    offs, _ = layout.padded_offsets(elem_bytes)
+    return [(n, flat[o : o + m].view(s)) for n, s, o, m in zip(layout.names, layout.shapes, offs, layout.numels)]
+
+
 def gather_client_samples(buckets: torch.Tensor, idx: torch.Tensor, first_client: int) -> tuple[np.ndarray, int]:
     """The sampled elements of every resident client row ([n, K] fp64, exact) and how many rows
     differ from their regeneration from the client's seed (make_clients): 0 = the inputs the
@@ -769,6 +818,11 @@ def main_personalized(args: argparse.Namespace) -> int:
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
     kernel_ms, launches = ctx.prof_collect()
+    if args.dump_outputs:  # every receiver's model, then the centralized average
+        dump_outputs(args.dump_outputs,
+                     [(f"receiver{j:03d}.{n}", v.view(s)) for j, row in enumerate(outs)
+                      for n, s, v in zip(layout.names, layout.shapes, row)]
+                     + [(f"central.{n}", v.view(s)) for n, s, v in zip(layout.names, layout.shapes, central)])
     step_s = elapsed / args.steps
     kstep_s = kernel_ms * 1e-3 / args.steps
     in_bytes = torch.empty((), dtype=in_dtype).element_size()
@@ -989,6 +1043,8 @@ def main_qsgd(args: argparse.Namespace) -> int:
     ctx.prof_enable(False)
     kernel_ms, launches = ctx.prof_collect()
     out_bytes = torch.empty((), dtype=out_dtype).element_size()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, layout_views(layout, out_flat, out_bytes))
     job_bytes = N * client_bytes + P * out_bytes  # every record byte the fold must read + the result
     step_s = elapsed / args.steps
     per_launch_s = kernel_ms * 1e-3 / max(launches, 1)
@@ -1112,7 +1168,10 @@ def main_plugin(args: argparse.Namespace) -> int:
         tail_s[0] += time.perf_counter() - t_last
         algo.clear_worker_data()
         assert len(res.parameter) == T and res.in_round == in_round
+        if args.dump_outputs:
+            last_result[0] = res.parameter
 
+    last_result: list = [None]
     for _ in range(args.warmup):
         step()
     ctx = algo._context()
@@ -1133,7 +1192,10 @@ def main_plugin(args: argparse.Namespace) -> int:
     dyn_ms, dyn_waves = ctx.dyn_prof_collect()
     dyn = {k: round((algo.dyn_stats[k] - dyn0[k]) / args.steps, 2) for k in dyn0}
     host_timed, tail_timed = host_s[0], tail_s[0]
-    if dyn_waves and not args.no_kernel_events:
+    if args.dump_outputs:  # the result dict aggregate_worker_data returned in the last timed round
+        dump_outputs(args.dump_outputs, [(n, last_result[0][n]) for n in layout.names])
+        last_result[0] = None
+    if args.full and dyn_waves and not args.no_kernel_events:
         # after the timed region: the same rounds again, each wave's tiles recording when they
         # finished (fedavg_dyn_timing, GPU clock): the fold after the last rows reached the tiles
         # (result stores included) and after the close, medians over the rounds
@@ -1170,8 +1232,8 @@ def main_plugin(args: argparse.Namespace) -> int:
     # the HBM probes (read / copy ceilings; their known byte counts calibrate a PMC pass's
     # FETCH_SIZE / WRITE_SIZE in the same process, scripts/dyn_traffic.sh)
     probe = None if args.no_probe else hbm_probes(device)
-    burst = None
-    if bursts > 1:
+    burst, burst_ms = None, None
+    if bursts > 1 and args.full:
         # one burst's clients folded by the one-launch kernel (HIP events): the fold time the
         # burst's latency is judged against (last arrival -> result <= 1.2x of it)
         bctx = FedAvgContext(layout, device)
@@ -1195,10 +1257,11 @@ def main_plugin(args: argparse.Namespace) -> int:
         del bplan
         bctx.close()
         burst_ms = b_ms / max(b_n, 1)
+    if bursts > 1:
         lat_ms = tail_s[0] / args.steps * 1e3
         burst = {"bursts": bursts, "updates_per_burst": per_burst, "gap_ms": gap_s * 1e3,
                  "last_arrival_to_result_ms": round(lat_ms, 4),
-                 "one_burst_fold_ms": round(burst_ms, 4),
+                 "one_burst_fold_ms": None if burst_ms is None else round(burst_ms, 4),
                  "ratio": round(lat_ms / burst_ms, 3) if burst_ms else None,
                  "what": "last process_worker_data returned -> aggregate_worker_data returned (result on the "
                          "device, NaN flags read), against one burst's clients folded and divided by the "
@@ -1444,34 +1507,41 @@ def main_multi(args: argparse.Namespace) -> int:
     step_s = elapsed / args.steps
     job_bytes = n_total * P * in_b + P * out_b
     value = job_bytes / step_s / 1e9
+    if args.dump_outputs:
+        _STAGES.enter("dump_outputs")
+        dump_outputs(args.dump_outputs, layout_views(layout, out_flat, out_b))
 
     # the result of the last timed round, sampled, against host fp64 compositions of the same
     # clients (and every client row against its regeneration from its seed)
-    _STAGES.enter("result_check")
-    picks = sample_elements(layout)
-    got = out_flat[flat_index(layout, picks, out_b, root_dev)].to(torch.float64).cpu().numpy()
-    shards, shard_w, changed = [], [], 0
-    for g, d in enumerate(devices):
-        lo, hi = shard_bounds(n_total, G, g)
-        s, c = gather_client_samples(keep[g], flat_index(layout, picks, in_b, torch.device("cuda", d)), lo)
-        shards.append(s)
-        shard_w.append(weights_all[lo:hi])
-        changed += c
-    check = result_check(got, shards, shard_w, args.out_dtype, "composition" if ex == "peer" else None)
-    check["client_rows_changed"] = changed
-    check["ok"] = check["ok"] and changed == 0
+    check = None
+    if args.full:
+        _STAGES.enter("result_check")
+        picks = sample_elements(layout)
+        got = out_flat[flat_index(layout, picks, out_b, root_dev)].to(torch.float64).cpu().numpy()
+        shards, shard_w, changed = [], [], 0
+        for g, d in enumerate(devices):
+            lo, hi = shard_bounds(n_total, G, g)
+            s, c = gather_client_samples(keep[g], flat_index(layout, picks, in_b, torch.device("cuda", d)), lo)
+            shards.append(s)
+            shard_w.append(weights_all[lo:hi])
+            changed += c
+        check = result_check(got, shards, shard_w, args.out_dtype, "composition" if ex == "peer" else None)
+        check["client_rows_changed"] = changed
+        check["ok"] = check["ok"] and changed == 0
 
     # the dominant kernel, after the timed region: entry 0's windowed partial launches (one per
     # chunk) timed with HIP events on its stream over the same number of rounds
-    _STAGES.enter("kernel_events")
-    ctx0 = m.contexts[0]
-    ctx0.prof_collect()
-    ctx0.prof_enable(not args.no_kernel_events)
-    for _ in range(args.steps):
-        one_round(ex, edges)
-    sync_all()
-    ctx0.prof_enable(False)
-    kernel_ms, launches = ctx0.prof_collect()
+    kernel_ms, launches = 0.0, 0
+    if args.full:
+        _STAGES.enter("kernel_events")
+        ctx0 = m.contexts[0]
+        ctx0.prof_collect()
+        ctx0.prof_enable(not args.no_kernel_events)
+        for _ in range(args.steps):
+            one_round(ex, edges)
+        sync_all()
+        ctx0.prof_enable(False)
+        kernel_ms, launches = ctx0.prof_collect()
     lo0, hi0 = shard_bounds(n_total, G, 0)
     rank_bytes = P * (hi0 - lo0) * in_b + P * 8  # its clients' reads + its fp64 partial stores (local or peer)
     kernel_step_ms = kernel_ms / args.steps
@@ -1479,14 +1549,16 @@ def main_multi(args: argparse.Namespace) -> int:
     predicted = model.round_ms(G, P, n_total, in_b, out_b, edges, ex) if G > 1 else None
     one_gpu = model.one_gpu_ms(P, n_total, in_b, out_b)
     # the exposed exchange + division tail, event-timed on entry 0 over the same number of rounds
-    _STAGES.enter("exchange_tail")
-    m.prof_collect()
-    m.prof_enable(True)
-    for _ in range(args.steps):
-        one_round(ex, edges)
-    sync_all()
-    m.prof_enable(False)
-    tail = m.prof_collect()
+    tail = None
+    if args.full:
+        _STAGES.enter("exchange_tail")
+        m.prof_collect()
+        m.prof_enable(True)
+        for _ in range(args.steps):
+            one_round(ex, edges)
+        sync_all()
+        m.prof_enable(False)
+        tail = m.prof_collect()
     _STAGES.enter("teardown")
     m.close()
     del partials
@@ -1532,7 +1604,7 @@ def main_multi(args: argparse.Namespace) -> int:
         "result_check": check,
         "cpu_baseline": None,
     }
-    if not check["ok"]:
+    if check is not None and not check["ok"]:
         # not on stdout: a fallback run prints the job's one line
         print(f"bench.py --procs 1: the result check failed; the line was: {json.dumps(line)}", file=sys.stderr,
               flush=True)
@@ -1607,6 +1679,10 @@ def main_elements(args: argparse.Namespace) -> int:
         dist.destroy_process_group()
     if rank != 0:
         return 0
+    if args.dump_outputs:
+        starts = np.cumsum([0] + layout.numels[:-1]).tolist()
+        dump_outputs(args.dump_outputs, [(n, out[o : o + k].view(s)) for n, s, o, k in
+                                         zip(layout.names, layout.shapes, starts, layout.numels)])
     in_b, out_b = torch.empty((), dtype=in_dtype).element_size(), torch.empty((), dtype=out_dtype).element_size()
     step_s = elapsed / args.steps
     job_bytes = n_total * P * in_b + P * out_b
@@ -1964,7 +2040,19 @@ def main() -> int:
                     help="launcher check without a GPU: every rank joins a gloo group, takes its client "
                          "shard and the max-over-ranks timing of an empty step; prints the JSON line "
                          "with value null (no measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the HBM probes, "
+                         "the sampled result check, the N > 1 line's one-GPU anchor and the untimed diagnostic "
+                         "rounds after the timed ones (--no-cpu-baseline, --no-probe, --no-anchor take theirs "
+                         "out again); a plain run leaves those keys of the line null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result of the last one as DIR/<tensor name>.npy "
+                         "(float32 / float64; at most 64 MB, a larger result as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_probe = args.no_anchor = True
     if args.out_dtype is None:
         args.out_dtype = "float64" if args.workload in ("plugin", "gradient") else "float32"
     if args.clients_per_gpu is None:
@@ -2133,34 +2221,39 @@ def main() -> int:
 
     in_bytes = torch.empty((), dtype=in_dtype).element_size()
     out_bytes = torch.empty((), dtype=out_dtype).element_size()
+    if args.dump_outputs and rank == 0:
+        if world > 1:
+            _STAGES.enter("dump_outputs")
+        dump_outputs(args.dump_outputs, layout_views(layout, out_flat, out_bytes))
     # the result of the last timed round, sampled (every tensor's ends + 4096 random elements),
     # against host fp64 compositions of the same clients; every client row is also compared with
     # its regeneration from its seed. Rank 0 checks; the other ranks send their shards' samples.
-    if world > 1:
-        _STAGES.enter("result_check")
-    picks = sample_elements(layout)
-    s_local, changed = gather_client_samples(buckets, flat_index(layout, picks, in_bytes, device), lo)
-    bounds = [shard_bounds(n_total, world, r) for r in range(world)]
-    if dist.is_initialized():
-        xdev = torch.device("cpu") if args.rehearse else device
-        n_max = max(b - a for a, b in bounds)
-        mine = torch.zeros((n_max, len(picks)), dtype=torch.float64, device=xdev)
-        mine[:n_local] = torch.from_numpy(s_local).to(xdev)
-        every = [torch.empty_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        ch = torch.tensor([changed], dtype=torch.int64, device=xdev)
-        dist.all_reduce(ch)
-        changed = int(ch.item())
-        shard_samples = [every[r][: b - a].cpu().numpy() for r, (a, b) in enumerate(bounds)]
-    else:
-        shard_samples = [s_local]
     check = None
-    if rank == 0:
-        got = out_flat[flat_index(layout, picks, out_bytes, device)].to(torch.float64).cpu().numpy()
-        check = result_check(got, shard_samples, [weights_all[a:b] for a, b in bounds], args.out_dtype,
-                             "single" if world == 1 else None)
-        check["client_rows_changed"] = changed
-        check["ok"] = check["ok"] and changed == 0
+    if args.full:
+        if world > 1:
+            _STAGES.enter("result_check")
+        picks = sample_elements(layout)
+        s_local, changed = gather_client_samples(buckets, flat_index(layout, picks, in_bytes, device), lo)
+        bounds = [shard_bounds(n_total, world, r) for r in range(world)]
+        if dist.is_initialized():
+            xdev = torch.device("cpu") if args.rehearse else device
+            n_max = max(b - a for a, b in bounds)
+            mine = torch.zeros((n_max, len(picks)), dtype=torch.float64, device=xdev)
+            mine[:n_local] = torch.from_numpy(s_local).to(xdev)
+            every = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            ch = torch.tensor([changed], dtype=torch.int64, device=xdev)
+            dist.all_reduce(ch)
+            changed = int(ch.item())
+            shard_samples = [every[r][: b - a].cpu().numpy() for r, (a, b) in enumerate(bounds)]
+        else:
+            shard_samples = [s_local]
+        if rank == 0:
+            got = out_flat[flat_index(layout, picks, out_bytes, device)].to(torch.float64).cpu().numpy()
+            check = result_check(got, shard_samples, [weights_all[a:b] for a, b in bounds], args.out_dtype,
+                                 "single" if world == 1 else None)
+            check["client_rows_changed"] = changed
+            check["ok"] = check["ok"] and changed == 0
 
     job_bytes = n_total * P * in_bytes + P * out_bytes
     step_s = elapsed / args.steps
@@ -2192,7 +2285,7 @@ def main() -> int:
     # partial-only rounds (the chunk kernels without the exchange), so the line shows how much
     # of the step is the exposed reduce tail + the root's finalize.
     partial_only_ms = None
-    pplan = getattr(reducer, "_partial_plan", None) if sharded else None
+    pplan = getattr(reducer, "_partial_plan", None) if sharded and args.full else None
     if world > 1:
         _STAGES.enter("partial_only")
     if pplan is not None:

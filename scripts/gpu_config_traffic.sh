@@ -11,7 +11,7 @@ mkdir -p $OUT
 IFS=';' read -ra CFGS <<< "$CONFIGS"
 for cfg in "${CFGS[@]}"; do
   name=${cfg%%:*}; args=${cfg#*:}
-  B="bench.py --no-cpu-baseline --steps ${STEPS:-5} --warmup 2 $args"
+  B="bench.py --full --no-cpu-baseline --steps ${STEPS:-5} --warmup 2 $args"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/${name}_trace -o run --output-format csv -- python3 $B > $OUT/${name}_trace.log 2>&1 || { echo "$name trace failed"; tail -20 $OUT/${name}_trace.log; exit 1; }
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -T -d $OUT/${name}_fetch -o run --output-format csv -- python3 $B > $OUT/${name}_fetch.log 2>&1 || { echo "$name fetch failed"; tail -20 $OUT/${name}_fetch.log; exit 1; }
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -T -d $OUT/${name}_write -o run --output-format csv -- python3 $B > $OUT/${name}_write.log 2>&1 || { echo "$name write failed"; tail -20 $OUT/${name}_write.log; exit 1; }

@@ -4,7 +4,7 @@
 # Steps (each under its own time limit, chained: the first failure ends the call):
 #   smoke                 __graft_entry__.smoke()
 #   tests[=<pytest args>] pytest -m gpu (default: the whole GPU suite; e.g. tests=tests/test_gpu_multi_device.py)
-#   bench                 the headline N=1 line (bench.py, default flags)
+#   bench                 the headline N=1 line with everything it can report (bench.py --full)
 #   alias<G>              the single-process peer round rehearsed with G aliased entries on cuda:0
 #   plugin / gradient     bench.py --workload plugin / gradient
 #   plugin_static / gradient_static   the same with the dynamic wave off (FEDAVG_DYN=0)
@@ -43,20 +43,20 @@ for step in "$@"; do
            tail -3 "$O/tests.log" ;;
     tests=*) run tests 900 python -u -m pytest -x -q --timeout 120 --timeout-method thread ${step#tests=}
              tail -3 "$O/tests.log" ;;
-    bench) run bench 400 python -u bench.py ;;
+    bench) run bench 400 python -u bench.py --full ;;
     alias*) G=${step#alias}
-            run alias$G 400 python -u bench.py --procs 1 --gpus "$G" --alias --no-probe --stage-timeout 200 ;;
-    plugin) run plugin 300 python -u bench.py --workload plugin --no-cpu-baseline ;;
-    gradient) run gradient 300 python -u bench.py --workload gradient --no-cpu-baseline ;;
-    plugin_static) FEDAVG_DYN=0 run plugin_static 300 python -u bench.py --workload plugin --no-cpu-baseline ;;
-    bursts) run bursts 300 python -u bench.py --workload plugin --no-cpu-baseline --arrival bursts:4:2 ;;
-    bursts_static) FEDAVG_DYN=0 run bursts_static 300 python -u bench.py --workload plugin --no-cpu-baseline --arrival bursts:4:2 ;;
-    bursts_spin) FEDAVG_DYN_IDLE_US=1000000 run bursts_spin 300 python -u bench.py --workload plugin --no-cpu-baseline --arrival bursts:4:2 ;;
+            run alias$G 400 python -u bench.py --full --procs 1 --gpus "$G" --alias --no-probe --stage-timeout 200 ;;
+    plugin) run plugin 300 python -u bench.py --full --workload plugin --no-cpu-baseline ;;
+    gradient) run gradient 300 python -u bench.py --full --workload gradient --no-cpu-baseline ;;
+    plugin_static) FEDAVG_DYN=0 run plugin_static 300 python -u bench.py --full --workload plugin --no-cpu-baseline ;;
+    bursts) run bursts 300 python -u bench.py --full --workload plugin --no-cpu-baseline --arrival bursts:4:2 ;;
+    bursts_static) FEDAVG_DYN=0 run bursts_static 300 python -u bench.py --full --workload plugin --no-cpu-baseline --arrival bursts:4:2 ;;
+    bursts_spin) FEDAVG_DYN_IDLE_US=1000000 run bursts_spin 300 python -u bench.py --full --workload plugin --no-cpu-baseline --arrival bursts:4:2 ;;
     idle=*) I=${step#idle=}
-            FEDAVG_DYN_IDLE_US=$I run plugin_idle$I 300 python -u bench.py --workload plugin --no-cpu-baseline
-            FEDAVG_DYN_IDLE_US=$I run gradient_idle$I 300 python -u bench.py --workload gradient --no-cpu-baseline ;;
-    cpu) run cpu 400 python -u bench.py --no-probe --steps 5 --warmup 2 ;;
-    gradient_static) FEDAVG_DYN=0 run gradient_static 300 python -u bench.py --workload gradient --no-cpu-baseline ;;
+            FEDAVG_DYN_IDLE_US=$I run plugin_idle$I 300 python -u bench.py --full --workload plugin --no-cpu-baseline
+            FEDAVG_DYN_IDLE_US=$I run gradient_idle$I 300 python -u bench.py --full --workload gradient --no-cpu-baseline ;;
+    cpu) run cpu 400 python -u bench.py --full --no-probe --steps 5 --warmup 2 ;;
+    gradient_static) FEDAVG_DYN=0 run gradient_static 300 python -u bench.py --full --workload gradient --no-cpu-baseline ;;
     pers_int) run pers_int 300 python -u bench.py --workload personalized --pers-weights int --no-cpu-baseline --no-probe ;;
     pers_float) run pers_float 300 python -u bench.py --workload personalized --pers-weights float --no-cpu-baseline --no-probe ;;
     profile) run profile 900 bash scripts/profile.sh "$TAG" ;;

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=${1:-r01}
 OUT=gpurun_out/prof_${TAG}_f64
 mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --in-dtype float64 --out-dtype float64 > $OUT/bench_trace.log 2>&1 || { echo "f64 trace pass failed"; tail -20 $OUT/bench_trace.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --in-dtype float64 --out-dtype float64 > $OUT/bench_trace.log 2>&1 || { echo "f64 trace pass failed"; tail -20 $OUT/bench_trace.log; exit 1; }
 cp $OUT/trace/run_kernel_stats.csv profiles/${TAG}_f64_kernel_stats.csv
 grep -h "^{\"metric\"" $OUT/bench_trace.log > profiles/${TAG}_f64_bench.json
 head -3 profiles/${TAG}_f64_kernel_stats.csv

@@ -1,5 +1,5 @@
 """bench.py helpers that run without a GPU: the pinned CPU baseline child, the committed-traffic
-lookups, the speed-up block (CPU)."""
+lookups, the speed-up block, the --dump-outputs writer (CPU)."""
 
 from __future__ import annotations
 
@@ -57,3 +57,38 @@ def test_committed_headline_traffic(bench):
     t, src = bench.committed_traffic(1, 64, "float32", "float32")
     assert t and src.startswith("profiles/r") and src.endswith("_traffic.json")
     assert bench.committed_traffic(2, 64, "float32", "float32") == (None, None)
+
+
+def test_dump_outputs_writes_small_results_whole(bench, tmp_path):
+    import numpy as np
+    import torch
+
+    named = [("a.weight", torch.arange(12, dtype=torch.float32).view(3, 4)),
+             ("b", torch.tensor(2.5, dtype=torch.float64)),
+             ("c.half", torch.ones(5, dtype=torch.float16))]
+    info = bench.dump_outputs(str(tmp_path / "out"), named)
+    assert info["arrays"] == 3 and not info["sampled"]
+    a, b, c = (np.load(tmp_path / "out" / f"{n}.npy") for n, _ in named)
+    assert a.dtype == np.float32 and a.shape == (3, 4) and np.array_equal(a, named[0][1].numpy())
+    assert b.dtype == np.float64 and b.shape == () and b == 2.5
+    assert c.dtype == np.float32 and np.array_equal(c, np.ones(5, np.float32))
+
+
+def test_dump_outputs_samples_a_large_result_the_same_way_every_time(bench, tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    g = torch.Generator().manual_seed(3)
+    named = [("big", torch.randn(5000, generator=g, dtype=torch.float64)),
+             ("small", torch.randn(7, generator=g)), ("one", torch.randn((), generator=g))]
+    first = bench.dump_outputs(str(tmp_path / "x"), named)
+    second = bench.dump_outputs(str(tmp_path / "y"), named)
+    assert first["sampled"] and first["bytes"] == second["bytes"]
+    on_disk = sum(p.stat().st_size for p in (tmp_path / "x").iterdir())
+    assert on_disk <= 4096
+    for n, t in named:
+        x, y = np.load(tmp_path / "x" / f"{n}.npy"), np.load(tmp_path / "y" / f"{n}.npy")
+        assert x.ndim == 1 and len(x) >= 1 and x.tobytes() == y.tobytes()
+        assert np.isin(x, t.reshape(-1).numpy()).all()  # elements of the tensor itself
+    assert len(np.load(tmp_path / "x" / "big.npy")) > 100
