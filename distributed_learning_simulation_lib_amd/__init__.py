@@ -6,7 +6,14 @@ HIP kernels behind the C ABI of ``include/fedavg_hip.h``; this package is the ho
 keeps the reference's plugin surface.
 """
 
-from .algorithm import AggregationAlgorithm, FedAVGAlgorithm, PersonalizedFedAVGAlgorithm
+import functools
+
+from .algorithm import (
+    AggregationAlgorithm,
+    FedAVGAlgorithm,
+    PersonalizedFedAVGAlgorithm,
+    RobustFedAVGAlgorithm,
+)
 from .algorithm_repository import AlgorithmRepository
 from .fedavg import ClientTable, FedAvgContext, ModelLayout, NaNAggregationError
 from .message import (
@@ -36,6 +43,7 @@ __all__ = [
     "ParameterMessage",
     "ParameterMessageBase",
     "PersonalizedFedAVGAlgorithm",
+    "RobustFedAVGAlgorithm",
     "get_message_size",
 ]
 
@@ -52,6 +60,17 @@ def _register_builtin() -> None:
             server_cls=AggregationServer,
             algorithm_cls=FedAVGAlgorithm,
         )
+    # the robust rules (not reference algorithms): the same server, another aggregation rule
+    for name, mode in (("fed_trimmed_mean", "trimmed_mean"), ("fed_median", "median")):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=functools.partial(RobustFedAVGAlgorithm, mode=mode),
+            )
 
 
 _register_builtin()

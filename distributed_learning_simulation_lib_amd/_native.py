@@ -35,6 +35,9 @@ MULTI_MAX_DEVICES = 16
 FLAG_ACC_NAN = 0x1
 FLAG_RESULT_NAN = 0x2
 FLAG_CENTRAL_NAN = 0x4
+FLAG_INPUT_NAN = 0x8  # robust rules: a client tensor holds NaN
+ROBUST_TRIMMED_MEAN, ROBUST_MEDIAN = 0, 1  # FEDAVG_ROBUST_*: fedavg_robust_aggregate modes
+ROBUST_MAX_CLIENTS = 64
 ABI_VERSION = 1
 ACC_ALIGN = 32  # FEDAVG_ACC_ALIGN: accumulator segments start at multiples of 32 elements
 BUILD_ABLATE_EPILOGUE = 0x1
@@ -115,6 +118,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_plan_finalize_window": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "fedavg_plan_copy_out": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fedavg_plan_out_dtype": (c_int32, [c_void_p]),
+    "fedavg_robust_aggregate": (
+        c_int32,
+        [c_void_p, _PP, c_int32, c_int32, c_int32, POINTER(c_int32), _PP, c_int32, c_void_p],
+    ),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

@@ -1,5 +1,6 @@
 from .aggregation_algorithm import AggregationAlgorithm
 from .fed_avg_algorithm import FedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
+from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 
-__all__ = ["AggregationAlgorithm", "FedAVGAlgorithm", "PersonalizedFedAVGAlgorithm"]
+__all__ = ["AggregationAlgorithm", "FedAVGAlgorithm", "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]

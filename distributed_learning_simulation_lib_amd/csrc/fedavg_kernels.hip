@@ -40,6 +40,7 @@
 
 #include "../../include/fedavg_hip.h"
 #include "exact_div.h"
+#include "robust_internal.h"
 
 namespace {
 
@@ -390,7 +391,7 @@ struct Geo {
 };
 
 // NaN flags live in host-coherent pinned memory, one word per condition (0: accumulator NaN,
-// 1: result NaN). A wave that sees a NaN stores 1 with system scope — no atomics, every
+// 1: result NaN, 2: input NaN — raised by the robust rules, robust_kernels.hip). A wave that sees a NaN stores 1 with system scope — no atomics, every
 // writer writes the same value — and the host reads the words after the stream drains.
 __device__ __forceinline__ void raise_flag(uint32_t* flag, int word) {
   __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -2239,6 +2240,8 @@ struct fedavg_ctx {
   size_t qtab_last_bytes = 0;                // table bytes of the last QSGD launch
   hipEvent_t aux_done = nullptr;  // the last upload out of aux_host finished
   bool aux_used = false;
+  // per-context state of the robust rules (robust_kernels.hip: tile table, table staging)
+  void* robust = nullptr;
   // the dynamic wave (fedavg_dyn_*): its host-coherent control block and row table, the device
   // mirror words, a private stream (the caller's stream stays free for the work producing the
   // arrivals) and the per-segment totals of the published rows
@@ -2943,7 +2946,7 @@ int32_t launch_main(fedavg_ctx* c, hipStream_t s, const Staged& st, int32_t in_d
 
 }  // namespace
 
-// Shared with the other translation units of the library (personalized_kernels.hip): one
+// Shared with the other translation units of the library (personalized / robust kernels): one
 // thread-local last-error string behind fedavg_last_error().
 __attribute__((visibility("hidden"))) int32_t fedavg_internal_fail(int32_t code, const char* msg) {
   return fail(code, msg);
@@ -3009,6 +3012,8 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
   else if (n == "nnadq_header") v = kNnadqHeader;
   else if (n.rfind("pers_", 0) == 0) {
     if (fedavg_internal_pers_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (n.rfind("robust_", 0) == 0) {
+    if (fedavg_internal_robust_constant(name, &v) != FEDAVG_OK) v = -1;
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);
@@ -3237,6 +3242,7 @@ int32_t fedavg_ctx_destroy(fedavg_ctx* c) {
   if (c->aux_host) (void)hipHostFree(c->aux_host);
   if (c->aux_dev) (void)hipFree(c->aux_dev);
   if (c->aux_done) (void)hipEventDestroy(c->aux_done);
+  if (c->robust) fedavg_internal_robust_release(c->device, c->robust);
   delete c;
   return FEDAVG_OK;
 }
@@ -3442,6 +3448,17 @@ int32_t fedavg_weighted_avg(fedavg_ctx* c, const void* const* client_ptrs, int32
   return launch_main(c, s, st, in_dtype, ok, split, 0, 0, static_cast<int32_t>(c->tiles1.size()));
 }
 
+int32_t fedavg_internal_robust_view(fedavg_ctx* c, fedavg_robust_view* out) {
+  FEDAVG_RET(check_ctx(c));
+  out->device = c->device;
+  out->num_segments = c->T;
+  out->seg_numel = c->seg_numel.data();
+  out->d_flag = c->d_flag;
+  out->busy = c->dyn.active ? 1 : 0;
+  out->state = &c->robust;
+  return FEDAVG_OK;
+}
+
 int32_t fedavg_num_tiles(const fedavg_ctx* c) {
   if (!c) return -1;
   return static_cast<int32_t>(c->tiles1.size());
@@ -3527,8 +3544,10 @@ int32_t fedavg_check(fedavg_ctx* c, void* stream, uint32_t* flags_out) {
   }
   FEDAVG_HIP_TRY(hipStreamSynchronize(s));
   const uint32_t f = (__atomic_load_n(&c->h_flag[0], __ATOMIC_ACQUIRE) ? FEDAVG_FLAG_ACC_NAN : 0u) |
-                     (__atomic_load_n(&c->h_flag[1], __ATOMIC_ACQUIRE) ? FEDAVG_FLAG_RESULT_NAN : 0u);
+                     (__atomic_load_n(&c->h_flag[1], __ATOMIC_ACQUIRE) ? FEDAVG_FLAG_RESULT_NAN : 0u) |
+                     (__atomic_load_n(&c->h_flag[2], __ATOMIC_ACQUIRE) ? FEDAVG_FLAG_INPUT_NAN : 0u);
   if (flags_out) *flags_out = f;
+  if (f & FEDAVG_FLAG_INPUT_NAN) return fail(FEDAVG_ERR_NAN_INPUT, "NaN in a client tensor");
   if (f & FEDAVG_FLAG_ACC_NAN) return fail(FEDAVG_ERR_NAN_ACCUM, "NaN in the accumulator");
   if (f & FEDAVG_FLAG_RESULT_NAN) return fail(FEDAVG_ERR_NAN_RESULT, "NaN in the aggregated result");
   return FEDAVG_OK;

@@ -15,6 +15,7 @@ arithmetic runs in the HIP kernels of ``csrc/fedavg_kernels.hip``; there is no C
 from __future__ import annotations
 
 import ctypes
+import math
 import weakref
 from collections.abc import Mapping, Sequence
 from dataclasses import dataclass
@@ -143,6 +144,42 @@ def out_code(dtype: torch.dtype) -> int:
         return OUT_CODES[dtype]
     except KeyError:
         raise TypeError(f"aggregated output dtype must be float32 or float64, not {dtype}") from None
+
+
+ROBUST_MODES = ("trimmed_mean", "median")
+
+
+def check_robust_rule(mode: str, trim: float) -> None:
+    """ValueError for an unknown robust rule or a trim fraction outside [0, 0.5)."""
+    if mode not in ROBUST_MODES:
+        raise ValueError(f"robust aggregation mode must be one of {ROBUST_MODES}, not {mode!r}")
+    if mode == "trimmed_mean" and not 0 <= trim < 0.5:  # NaN fails it too
+        raise ValueError(f"trim must satisfy 0 <= trim < 0.5 (the kept range must not be empty), not {trim}")
+
+
+def robust_trim(mode: str, trim: float, n: int) -> int:
+    """Values dropped at each end of a tensor's n sorted client values: floor(trim * n) for the
+    trimmed mean; (n - 1) // 2 for the median, which leaves the one or two middle values."""
+    return (n - 1) // 2 if mode == "median" else math.floor(trim * n)
+
+
+def robust_trim_counts(table: ClientTable, mode: str, trim: float) -> list[int]:
+    """Per segment k for the table's clients, after the refusals that need no device."""
+    check_robust_rule(mode, trim)
+    if table.num_clients == 0:
+        raise ValueError("robust aggregation of no clients")
+    T = table.num_segments
+    sent = (np.asarray(table.arrays()[0]).reshape(table.num_clients, T) != 0).sum(axis=0)
+    ks = []
+    for t, n in enumerate(int(x) for x in sent):
+        if n > _native.ROBUST_MAX_CLIENTS:
+            raise NotImplementedError(
+                f"tensor {t} was sent by {n} clients: the register-resident sort holds at most "
+                f"{_native.ROBUST_MAX_CLIENTS} values per element")
+        if n == 0:
+            raise ValueError(f"tensor {t} was sent by no client")
+        ks.append(robust_trim(mode, trim, n))
+    return ks
 
 
 class ClientTable:
@@ -529,6 +566,36 @@ class FedAvgContext:
             )
         )
 
+    def robust_aggregate(
+        self,
+        table: ClientTable,
+        in_dtype: torch.dtype,
+        mode: str,
+        trim: float,
+        outs: Sequence[torch.Tensor] | OutputTable,
+        out_dtype: torch.dtype = torch.float64,
+    ) -> None:
+        """Coordinate-wise trimmed mean (``mode="trimmed_mean"``, 0 <= trim < 0.5) or median
+        (``mode="median"``) of the table's clients, one launch (``fedavg_robust_aggregate``; not a
+        reference algorithm, DESIGN.md "Robust rules"). Per tensor the n clients that sent it count,
+        k = floor(trim * n) values are dropped at each end; the table's weights are ignored — both
+        rules are unweighted. Refused before any launch: ``trim`` outside [0, 0.5), a tensor sent
+        by more than 64 clients, quantised records."""
+        k_per_seg = robust_trim_counts(table, mode, trim)
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("robust aggregation reads dense tensors: dequantise records first")
+        self._check_table(table, in_dtype)
+        p, _ = table.arrays()
+        ot = self._out_table(outs, out_dtype)
+        ks = (ctypes.c_int32 * self.layout.num_segments)(*k_per_seg)
+        _native.check(
+            self._lib.fedavg_robust_aggregate(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), table.num_clients,
+                _native.ROBUST_MEDIAN if mode == "median" else _native.ROBUST_TRIMMED_MEAN, ks, ot,
+                out_code(out_dtype), self.stream,
+            )
+        )
+
     def partial(
         self,
         table: ClientTable | None,
@@ -713,7 +780,7 @@ class FedAvgContext:
         """Synchronise the stream and return the latched NaN flag bits."""
         f = ctypes.c_uint32()
         st = self._lib.fedavg_check(self._h, self.stream, ctypes.byref(f))
-        if st not in (_native.OK, _native.ERR_NAN_ACCUM, _native.ERR_NAN_RESULT):
+        if st not in (_native.OK, _native.ERR_NAN_INPUT, _native.ERR_NAN_ACCUM, _native.ERR_NAN_RESULT):
             _native.check(st)
         return int(f.value)
 
@@ -739,6 +806,12 @@ class FedAvgContext:
             return
         # the flag is sticky until reset: clear it so the context stays usable
         self.reset()
+        if f & _native.FLAG_INPUT_NAN:  # the robust rules check their inputs in the same pass
+            for table, dt in tables:
+                bad = self.find_nan_clients(table, dt)
+                if bad:
+                    raise NaNAggregationError("input", f"NaN in client update(s) at table rows {bad}", bad)
+            raise NaNAggregationError("input", "NaN in a client update")
         if f & _native.FLAG_ACC_NAN:
             for table, dt in tables:
                 bad = self.find_nan_clients(table, dt)

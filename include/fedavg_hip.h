@@ -100,6 +100,7 @@ enum fedavg_status {
 #define FEDAVG_FLAG_ACC_NAN 0x1u
 #define FEDAVG_FLAG_RESULT_NAN 0x2u
 #define FEDAVG_FLAG_CENTRAL_NAN 0x4u /* personalized path: the centralized average */
+#define FEDAVG_FLAG_INPUT_NAN 0x8u   /* robust rules: a client tensor holds NaN */
 
 typedef struct fedavg_ctx fedavg_ctx;
 
@@ -122,7 +123,9 @@ int32_t fedavg_build_flags(void);
  * (clients loaded per group), "pipe_<d>" (clients per pipeline stage, 0 = no pipeline);
  * "qsgd_tile", "qsgd_ae", "qsgd_group"; "nnadq_tile", "nnadq_ae", "nnadq_group",
  * "nnadq_header"; "pers_chunk", "pers_jb" (receivers per wave),
- * "pers_group" (receivers per launch), "pers_u", "pers_ring_stage", "pers_ring_depth".
+ * "pers_group" (receivers per launch), "pers_u", "pers_ring_stage", "pers_ring_depth";
+ * "robust_tile", "robust_lanes", "robust_max_clients" and "robust_ae_<d>" (elements of one 16-byte
+ * load: what a lane sorts per pass over its tile) of fedavg_robust_aggregate.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -318,8 +321,35 @@ int32_t fedavg_plan_copy_out(fedavg_plan* finalize, const void* res, void* strea
 int32_t fedavg_plan_out_dtype(const fedavg_plan* plan); /* FEDAVG_F32 / FEDAVG_F64; -1 if none */
 
 /*
- * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_ACCUM or
- * FEDAVG_ERR_NAN_RESULT. *flags_out (optional) receives the raw flag bits.
+ * Robust aggregation rules: the coordinate-wise trimmed mean and median of the clients' updates.
+ * NOT an algorithm of the reference (it has none besides the weighted mean): the contract is
+ * DESIGN.md "Robust rules", restated independently in tests/robust_reference.py.
+ *
+ * Per segment t, the n_t non-NULL entries of column t of client_ptrs[num_clients][num_segments]
+ * count (1 <= n_t <= 64: each lane sorts an element's n_t values in registers). Per element the
+ * values, converted exactly to fp64, are sorted in the IEEE total order (-inf < ... < -0.0 < +0.0
+ * < ... < +inf) into s_0 <= ... <= s_{n-1}; with k = trim_k[t] (0 <= 2k < n_t) the result is
+ *   (s_k + s_{k+1} + ... + s_{n-k-1}) / (n - 2k)
+ * summed in ascending order from s_k, every add rounded in fp64 (no FMA), IEEE division.
+ * mode FEDAVG_ROBUST_MEDIAN is that with k = (n_t - 1) / 2 (trim_k is ignored and may be NULL):
+ * s_{(n-1)/2} for odd n, (s_{n/2-1} + s_{n/2}) / 2.0 for even n. No weights: both rules are
+ * unweighted. out_ptrs[num_segments]: FEDAVG_F64, or FEDAVG_F32 = that fp64 result rounded to
+ * nearest even. One launch over the whole layout; the accumulator is not touched. A NaN input
+ * latches FEDAVG_FLAG_INPUT_NAN, a NaN result (+inf and -inf both kept) FEDAVG_FLAG_RESULT_NAN;
+ * fedavg_check reports them. in_dtype: FEDAVG_F32 / F16 / BF16 / F64 (no records, no deltas).
+ * FEDAVG_ERR_INVALID (bad mode / dtype / k, more than 64 clients for a segment, NULL tables),
+ * FEDAVG_ERR_STATE (a segment no client sent; an open dynamic wave) — all before any launch.
+ */
+#define FEDAVG_ROBUST_TRIMMED_MEAN 0
+#define FEDAVG_ROBUST_MEDIAN 1
+#define FEDAVG_ROBUST_MAX_CLIENTS 64
+int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                                int32_t num_clients, int32_t mode, const int32_t* trim_k,
+                                void* const* out_ptrs, int32_t out_dtype, void* stream);
+
+/*
+ * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
+ * FEDAVG_ERR_NAN_ACCUM or FEDAVG_ERR_NAN_RESULT. *flags_out (optional) receives the raw flag bits.
  */
 int32_t fedavg_check(fedavg_ctx* ctx, void* stream, uint32_t* flags_out);
 
