@@ -11,6 +11,7 @@ import functools
 from .algorithm import (
     AggregationAlgorithm,
     FedAVGAlgorithm,
+    KrumFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
 )
@@ -35,6 +36,7 @@ __all__ = [
     "FeatureMessage",
     "FedAVGAlgorithm",
     "FedAvgContext",
+    "KrumFedAVGAlgorithm",
     "Message",
     "ModelLayout",
     "ModelParameter",
@@ -70,6 +72,17 @@ def _register_builtin() -> None:
                 client_cls=None,  # type: ignore[arg-type]
                 server_cls=AggregationServer,
                 algorithm_cls=functools.partial(RobustFedAVGAlgorithm, mode=mode),
+            )
+    # Krum (one client kept) and Multi-Krum (num_selected=None: n - f clients, resolved per round)
+    for name, selected in (("krum", 1), ("multi_krum", None)):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=functools.partial(KrumFedAVGAlgorithm, num_selected=selected),
             )
 
 

@@ -38,6 +38,7 @@ FLAG_CENTRAL_NAN = 0x4
 FLAG_INPUT_NAN = 0x8  # robust rules: a client tensor holds NaN
 ROBUST_TRIMMED_MEAN, ROBUST_MEDIAN = 0, 1  # FEDAVG_ROBUST_*: fedavg_robust_aggregate modes
 ROBUST_MAX_CLIENTS = 64
+KRUM_MAX_CLIENTS = 256  # FEDAVG_KRUM_MAX_CLIENTS: fedavg_pairwise_sqdist
 ABI_VERSION = 1
 ACC_ALIGN = 32  # FEDAVG_ACC_ALIGN: accumulator segments start at multiples of 32 elements
 BUILD_ABLATE_EPILOGUE = 0x1
@@ -122,6 +123,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         c_int32,
         [c_void_p, _PP, c_int32, c_int32, c_int32, POINTER(c_int32), _PP, c_int32, c_void_p],
     ),
+    "fedavg_pairwise_sqdist": (c_int32, [c_void_p, _PP, c_int32, c_int32, c_void_p, c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

@@ -1,6 +1,8 @@
 from .aggregation_algorithm import AggregationAlgorithm
 from .fed_avg_algorithm import FedAVGAlgorithm
+from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 
-__all__ = ["AggregationAlgorithm", "FedAVGAlgorithm", "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]
+__all__ = ["AggregationAlgorithm", "FedAVGAlgorithm", "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
+           "RobustFedAVGAlgorithm"]

@@ -41,6 +41,7 @@
 #include "../../include/fedavg_hip.h"
 #include "exact_div.h"
 #include "robust_internal.h"
+#include "krum_internal.h"
 
 namespace {
 
@@ -2242,6 +2243,8 @@ struct fedavg_ctx {
   bool aux_used = false;
   // per-context state of the robust rules (robust_kernels.hip: tile table, table staging)
   void* robust = nullptr;
+  // per-context state of the pairwise distances (krum_kernels.hip: chunk table, workspace)
+  void* krum = nullptr;
   // the dynamic wave (fedavg_dyn_*): its host-coherent control block and row table, the device
   // mirror words, a private stream (the caller's stream stays free for the work producing the
   // arrivals) and the per-segment totals of the published rows
@@ -3014,6 +3017,8 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
     if (fedavg_internal_pers_constant(name, &v) != FEDAVG_OK) v = -1;
   } else if (n.rfind("robust_", 0) == 0) {
     if (fedavg_internal_robust_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (n.rfind("krum_", 0) == 0) {
+    if (fedavg_internal_krum_constant(name, &v) != FEDAVG_OK) v = -1;
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);
@@ -3243,6 +3248,7 @@ int32_t fedavg_ctx_destroy(fedavg_ctx* c) {
   if (c->aux_dev) (void)hipFree(c->aux_dev);
   if (c->aux_done) (void)hipEventDestroy(c->aux_done);
   if (c->robust) fedavg_internal_robust_release(c->device, c->robust);
+  if (c->krum) fedavg_internal_krum_release(c->device, c->krum);
   delete c;
   return FEDAVG_OK;
 }
@@ -3456,6 +3462,12 @@ int32_t fedavg_internal_robust_view(fedavg_ctx* c, fedavg_robust_view* out) {
   out->d_flag = c->d_flag;
   out->busy = c->dyn.active ? 1 : 0;
   out->state = &c->robust;
+  return FEDAVG_OK;
+}
+
+int32_t fedavg_internal_krum_slot(fedavg_ctx* c, void*** slot) {
+  FEDAVG_RET(check_ctx(c));
+  *slot = &c->krum;
   return FEDAVG_OK;
 }
 

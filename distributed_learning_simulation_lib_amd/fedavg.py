@@ -182,6 +182,36 @@ def robust_trim_counts(table: ClientTable, mode: str, trim: float) -> list[int]:
     return ks
 
 
+def krum_select(D: Any, f: int, m: int) -> tuple[list[float], list[int]]:
+    """Krum scores and the one-shot Multi-Krum choice from the n x n matrix of squared distances
+    (host arithmetic in fp64, shared by the GPU and the CPU path).
+
+    ``f`` is the assumed number of Byzantine clients (``n >= 2f + 3``). ``score_i`` is the sum of
+    the ``n - f - 2`` smallest ``D[i][j]``, ``j != i``: sorted ascending, ties in ascending ``j``,
+    added sequentially from the smallest. The ``m`` rows (``1 <= m <= n - f``; 1 is Krum) with the
+    smallest ``(score, row)`` are chosen, so ties go to the earlier arrival. Returns
+    ``(scores, chosen_rows)``, the rows in ascending order (arrival order)."""
+    rows = [[float(x) for x in r] for r in (D.tolist() if hasattr(D, "tolist") else D)]
+    n = len(rows)
+    if any(len(r) != n for r in rows):
+        raise ValueError("the distance matrix must be square")
+    f, m = int(f), int(m)
+    if f < 0 or n < 2 * f + 3:
+        raise ValueError(f"Krum needs n >= 2f + 3 clients: n = {n}, f = {f}")
+    if not 1 <= m <= n - f:
+        raise ValueError(f"Multi-Krum selects 1 <= m <= n - f = {n - f} clients, not {m}")
+    keep = n - f - 2
+    scores = []
+    for i, r in enumerate(rows):
+        near = sorted((d, j) for j, d in enumerate(r) if j != i)[:keep]
+        s = 0.0
+        for d, _ in near:
+            s = s + d
+        scores.append(s)
+    order = sorted(range(n), key=lambda i: (scores[i], i))
+    return scores, sorted(order[:m])
+
+
 class ClientTable:
     """Row-major [num_clients][num_segments] device pointers + fp64 weights for one call.
 
@@ -595,6 +625,35 @@ class FedAvgContext:
                 out_code(out_dtype), self.stream,
             )
         )
+
+    def pairwise_sqdist(self, table: ClientTable, in_dtype: torch.dtype) -> torch.Tensor:
+        """The n x n fp64 matrix (on the device) of squared distances between the table's clients'
+        whole updates, ``D[i][j] = sum_e (x_i[e] - x_j[e])^2`` in fp64 (``fedavg_pairwise_sqdist``;
+        not a reference algorithm): the device half of Krum. Exactly symmetric, +0.0
+        on the diagonal, the same bits on every run. The table's weights are ignored and the
+        accumulator is not touched. Refused before any launch: an empty table, more than 256
+        clients, an absent entry (distances compare whole updates), quantised records."""
+        if table.num_clients == 0:
+            raise ValueError("pairwise distances of no clients")
+        if table.num_clients > _native.KRUM_MAX_CLIENTS:
+            raise NotImplementedError(
+                f"{table.num_clients} clients: pairwise distances take at most {_native.KRUM_MAX_CLIENTS}")
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("pairwise distances read dense tensors: dequantise records first")
+        self._check_table(table, in_dtype)
+        p, _ = table.arrays()
+        absent = np.argwhere(np.asarray(p).reshape(table.num_clients, table.num_segments) == 0)
+        if len(absent):
+            k, t = (int(x) for x in absent[0])
+            raise ValueError(f"client {k} lacks tensor {t}: distances compare whole updates")
+        n = table.num_clients
+        out = torch.empty((n, n), dtype=torch.float64, device=self.device)
+        _native.check(
+            self._lib.fedavg_pairwise_sqdist(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, ctypes.c_void_p(out.data_ptr()), self.stream,
+            )
+        )
+        return out
 
     def partial(
         self,

@@ -125,7 +125,10 @@ int32_t fedavg_build_flags(void);
  * "nnadq_header"; "pers_chunk", "pers_jb" (receivers per wave),
  * "pers_group" (receivers per launch), "pers_u", "pers_ring_stage", "pers_ring_depth";
  * "robust_tile", "robust_lanes", "robust_max_clients" and "robust_ae_<d>" (elements of one 16-byte
- * load: what a lane sorts per pass over its tile) of fedavg_robust_aggregate.
+ * load: what a lane sorts per pass over its tile) of fedavg_robust_aggregate;
+ * "krum_chunk" (elements per workgroup), "krum_tile" (elements staged per step), "krum_block"
+ * (clients per row / column block), "krum_reg" (edge of a lane's pair block), "krum_threads",
+ * "krum_max_clients" and "krum_ae_<d>" (elements of one 16-byte load) of fedavg_pairwise_sqdist.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -346,6 +349,33 @@ int32_t fedavg_plan_out_dtype(const fedavg_plan* plan); /* FEDAVG_F32 / FEDAVG_F
 int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
                                 int32_t num_clients, int32_t mode, const int32_t* trim_k,
                                 void* const* out_ptrs, int32_t out_dtype, void* stream);
+
+/*
+ * Pairwise squared distances between the clients' whole updates: the device half of Krum and
+ * Multi-Krum (scores and selection are host arithmetic on the n x n result). NOT an algorithm of
+ * the reference: the contract is DESIGN.md §5h, restated independently in tests/krum_reference.py.
+ *
+ * client_ptrs[num_clients][num_segments], every entry non-NULL (distances compare whole updates).
+ *   out[i * n + j] = sum over every element e of every segment of (x_i[e] - x_j[e])^2
+ * with each value converted exactly to fp64, one fp64 subtraction, and the square and add in fp64
+ * (an FMA): never the norm / inner-product form, which cancels for updates that share a model.
+ * All terms are non-negative, so each entry is within (P + 2) * 2^-53 relative of the exact value
+ * (P = the layout's element count) whatever the order. The order is fixed all the same: within a
+ * chunk of "krum_chunk" elements of a segment ascending element order into one accumulator per
+ * pair, then the chunks in layout order; it depends on the layout only, never on the device or on
+ * timing (no floating-point atomics), so the same inputs give the same bits. out is exactly
+ * symmetric (i < j is computed and mirrored) with a +0.0 diagonal; num_clients == 1 writes one +0.0.
+ * `out` is device memory, n * n doubles. Asynchronous on `stream`; the accumulator is not touched.
+ * A NaN input latches FEDAVG_FLAG_INPUT_NAN (tested at the load). +inf / -inf inputs are legal
+ * (that client's distances are +inf); two clients with a same-signed infinity in the same element
+ * give inf - inf, which latches FEDAVG_FLAG_ACC_NAN. fedavg_check reports the flags.
+ * in_dtype: FEDAVG_F32 / F16 / BF16 / F64 (no records, no deltas). Refused before any launch:
+ * FEDAVG_ERR_INVALID (NULL table, entry or out; bad dtype; num_clients < 1 or >
+ * FEDAVG_KRUM_MAX_CLIENTS), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_KRUM_MAX_CLIENTS 256
+int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                               int32_t num_clients, double* out /* [n][n], device */, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
