@@ -1,11 +1,14 @@
 """Krum / Multi-Krum without a GPU: hand-computed answers for the torch restatement
 (tests/krum_reference.py) and for ``krum_select``, and ``KrumFedAVGAlgorithm`` on the CPU device
 against the restatement and, bit for bit, against the FedAvg oracle run on the chosen messages.
-Neither rule is a reference algorithm; the restatement is what parity means."""
+Neither rule is a reference algorithm; the restatement is what parity means.
+The last section checks the order-exact restatement itself: that its data can tell the contract's
+summation order from others, which is what makes the GPU comparison with it worth something."""
 
 from __future__ import annotations
 
 import math
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -17,6 +20,7 @@ from distributed_learning_simulation_lib_amd import (
     KrumFedAVGAlgorithm,
     NaNAggregationError,
     ParameterMessage,
+    _native,
 )
 from distributed_learning_simulation_lib_amd.fedavg import krum_select
 from distributed_learning_simulation_lib_amd.quantized import QuantizedTensor
@@ -283,3 +287,112 @@ def test_registration_names_resolve():
         assert entry.get("client_cls") is AlgorithmRepository.config["fed_trimmed_mean"].get("client_cls")
         algo = entry["algorithm_cls"]()
         assert isinstance(algo, KrumFedAVGAlgorithm) and algo.num_selected == selected and not algo.weighted
+
+
+# ---- the order-exact restatement: can its data tell one summation order from another? -----------
+# tests/test_gpu_krum_contract.py compares the kernel bit for bit with ``ref.distances_in_order`` on
+# ``ref.order_sensitive_values``. That is worth something only if (a) the kernel's FMA and the
+# restatement's multiply-then-add agree, i.e. every square is exact, and (b) another order would
+# give other bits. Both are conditions on the inputs and are established here, on the layouts of
+# that module's order test at n = 17.
+ORDER_DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f64": torch.float64}
+ORDER_N = 17
+
+
+def order_case(code, n=ORDER_N):
+    """(sizes, chunk, rows of float64 tensors): the layout and the data of the GPU module's order
+    test (same sizes, same seed)."""
+    from tests.test_gpu_krum_contract import order_layout, order_rows
+
+    sizes = order_layout(code)
+    return sizes, _native.kernel_constant("krum_chunk"), order_rows(n, sizes)
+
+
+def bits_differ(a, b) -> int:
+    """Pairs i < j whose entries differ in bits."""
+    iu, ju = np.triu_indices(a.shape[0], 1)
+    x = a.contiguous().view(torch.int64).numpy()[iu, ju]
+    y = b.contiguous().view(torch.int64).numpy()[iu, ju]
+    return int((x != y).sum())
+
+
+def reversed_partials(rows, chunk):
+    """A wrong order: the chunk partials added from the last chunk to the first."""
+    partials, iu, ju = ref.chunk_partials(rows, chunk)
+    total = np.zeros(len(iu))
+    for p in partials[::-1]:
+        total = total + p
+    D = torch.zeros((len(rows), len(rows)), dtype=torch.float64)
+    D[iu, ju] = torch.from_numpy(total)
+    return D + D.t()
+
+
+def two_accumulators(rows, chunk):
+    """A wrong order: a chunk's even and odd elements in two accumulators, added at its end."""
+    n = len(rows)
+    iu, ju = np.triu_indices(n, 1)
+    total = np.zeros(len(iu))
+    for t in range(len(rows[0])):
+        x = np.stack([r[t].to(torch.float64).numpy() for r in rows], axis=1)
+        for start in range(0, x.shape[0], chunk):
+            acc = [np.zeros(len(iu)), np.zeros(len(iu))]
+            for e, row in enumerate(x[start:start + chunk]):
+                d = row[iu] - row[ju]
+                acc[e % 2] = acc[e % 2] + d * d
+            total = total + (acc[0] + acc[1])
+    D = torch.zeros((n, n), dtype=torch.float64)
+    D[iu, ju] = torch.from_numpy(total)
+    return D + D.t()
+
+
+@pytest.mark.parametrize("code", list(ORDER_DTYPES))
+def test_order_sensitive_values_are_exact_in_every_format(code):
+    sizes, _, rows = order_case(code)
+    flat = torch.cat([torch.cat(r) for r in rows])
+    assert flat.dtype == torch.float64 and bool(torch.isfinite(flat).all()) and bool((flat != 0).all())
+    for dtype in ORDER_DTYPES.values():   # the drawn values round-trip through all four formats
+        assert bits(flat.to(dtype).to(torch.float64)) == bits(flat), dtype
+    # every square of a difference is exact: 2000 element pairs of random clients, as rationals
+    gen = torch.Generator().manual_seed(5)
+    P = sum(sizes)
+    x = torch.stack([torch.cat(r) for r in rows])
+    e = torch.randint(0, P, (2000,), generator=gen)
+    i = torch.randint(0, ORDER_N, (2000,), generator=gen)
+    j = (i + 1 + torch.randint(0, ORDER_N - 1, (2000,), generator=gen)) % ORDER_N
+    for a, b in zip(x[i, e].tolist(), x[j, e].tolist()):
+        d = a - b
+        assert Fraction(a) - Fraction(b) == Fraction(d)
+        assert Fraction(d) * Fraction(d) == Fraction(d * d)
+
+
+@pytest.mark.parametrize("code", list(ORDER_DTYPES))
+def test_in_order_restatement_tells_orders_apart(code):
+    sizes, chunk, rows = order_case(code)
+    pairs = ORDER_N * (ORDER_N - 1) // 2
+    D = ref.distances_in_order(rows, chunk)
+    assert D.dtype == torch.float64 and D.shape == (ORDER_N, ORDER_N)
+    assert bits(D) == bits(D.t().contiguous()) and not any(bits(torch.diagonal(D)))
+    plain = ref.distances(rows)
+    one_chunk = ref.distances_in_order([[torch.cat(r)] for r in rows], sum(sizes))   # no chunk boundary
+    k_plain, k_one = bits_differ(D, plain), bits_differ(D, one_chunk)
+    k_rev, k_two = bits_differ(D, reversed_partials(rows, chunk)), bits_differ(D, two_accumulators(rows, chunk))
+    print(f"{code}: sizes {sizes}: distances_in_order differs in bits from ref.distances in {k_plain} of {pairs} "
+          f"pairs, from the no-chunk variant in {k_one}, from reversed chunk partials in {k_rev}, "
+          f"from two interleaved accumulators in {k_two}")
+    assert 2 * k_plain >= pairs
+    assert k_one >= 1
+    assert k_rev >= 1 and k_two >= 1     # a kernel with either wrong order would fail the GPU test
+    # and it is a summation of the same terms: within the contract's bound of the plain restatement
+    bound = 2 * (sum(sizes) + 2) * 2.0 ** -53
+    assert bool(((D - plain).abs() <= bound * plain).all())
+
+
+def test_fused_restatement_agrees_where_squares_are_exact_and_differs_elsewhere():
+    gen = torch.Generator().manual_seed(11)
+    sizes, chunk = [5, 70, 3], 32
+    rows = [[ref.order_sensitive_values(gen, s) for s in sizes] for _ in range(4)]
+    assert bits(ref.distances_in_order_fused(rows, chunk)) == bits(ref.distances_in_order(rows, chunk))
+    rows = [[torch.randn(s, generator=gen, dtype=torch.float64) for s in sizes] for _ in range(4)]
+    fused, plain = ref.distances_in_order_fused(rows, chunk), ref.distances_in_order(rows, chunk)
+    assert bits_differ(fused, plain) >= 1     # N(0, 1): the FMA's single rounding shows
+    assert bool(((fused - plain).abs() <= 2 * (sum(sizes) + 2) * 2.0 ** -53 * plain).all())
