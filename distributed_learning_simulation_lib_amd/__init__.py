@@ -11,6 +11,7 @@ import functools
 from .algorithm import (
     AggregationAlgorithm,
     FedAVGAlgorithm,
+    GeometricMedianFedAVGAlgorithm,
     KrumFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
@@ -36,6 +37,7 @@ __all__ = [
     "FeatureMessage",
     "FedAVGAlgorithm",
     "FedAvgContext",
+    "GeometricMedianFedAVGAlgorithm",
     "KrumFedAVGAlgorithm",
     "Message",
     "ModelLayout",
@@ -84,6 +86,16 @@ def _register_builtin() -> None:
                 server_cls=AggregationServer,
                 algorithm_cls=functools.partial(KrumFedAVGAlgorithm, num_selected=selected),
             )
+    # the geometric median (RFA): smoothed Weiszfeld iterations over the same server
+    if not AlgorithmRepository.has_algorithm("fed_geometric_median"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_geometric_median",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=GeometricMedianFedAVGAlgorithm,
+        )
 
 
 _register_builtin()

@@ -42,6 +42,7 @@
 #include "exact_div.h"
 #include "robust_internal.h"
 #include "krum_internal.h"
+#include "point_internal.h"
 
 namespace {
 
@@ -2245,6 +2246,8 @@ struct fedavg_ctx {
   void* robust = nullptr;
   // per-context state of the pairwise distances (krum_kernels.hip: chunk table, workspace)
   void* krum = nullptr;
+  // per-context state of the distances to a point (point_kernels.hip: chunk table, workspace)
+  void* point = nullptr;
   // the dynamic wave (fedavg_dyn_*): its host-coherent control block and row table, the device
   // mirror words, a private stream (the caller's stream stays free for the work producing the
   // arrivals) and the per-segment totals of the published rows
@@ -3019,6 +3022,8 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
     if (fedavg_internal_robust_constant(name, &v) != FEDAVG_OK) v = -1;
   } else if (n.rfind("krum_", 0) == 0) {
     if (fedavg_internal_krum_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (n.rfind("point_", 0) == 0) {
+    if (fedavg_internal_point_constant(name, &v) != FEDAVG_OK) v = -1;
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);
@@ -3249,6 +3254,7 @@ int32_t fedavg_ctx_destroy(fedavg_ctx* c) {
   if (c->aux_done) (void)hipEventDestroy(c->aux_done);
   if (c->robust) fedavg_internal_robust_release(c->device, c->robust);
   if (c->krum) fedavg_internal_krum_release(c->device, c->krum);
+  if (c->point) fedavg_internal_point_release(c->device, c->point);
   delete c;
   return FEDAVG_OK;
 }
@@ -3468,6 +3474,12 @@ int32_t fedavg_internal_robust_view(fedavg_ctx* c, fedavg_robust_view* out) {
 int32_t fedavg_internal_krum_slot(fedavg_ctx* c, void*** slot) {
   FEDAVG_RET(check_ctx(c));
   *slot = &c->krum;
+  return FEDAVG_OK;
+}
+
+int32_t fedavg_internal_point_slot(fedavg_ctx* c, void*** slot) {
+  FEDAVG_RET(check_ctx(c));
+  *slot = &c->point;
   return FEDAVG_OK;
 }
 

@@ -212,6 +212,29 @@ def krum_select(D: Any, f: int, m: int) -> tuple[list[float], list[int]]:
     return scores, sorted(order[:m])
 
 
+def geometric_median_step(dist_sq: Sequence[float], alpha: Sequence[float],
+                          smoothing: float) -> tuple[list[float], float]:
+    """One smoothed Weiszfeld step of the geometric median (host arithmetic in plain
+    Python floats, shared by the GPU and the CPU path): from the clients' squared distances ``D_i``
+    to the current point and their weights ``alpha_i``, with ``d_i = math.sqrt(D_i)``, the next
+    fold's weights ``beta_i = alpha_i / max(smoothing, d_i)`` and the objective
+    ``sum_i alpha_i * d_i`` at the current point, added sequentially in arrival order from 0.0.
+    Returns ``(beta, objective)``."""
+    ds = [float(x) for x in (dist_sq.tolist() if hasattr(dist_sq, "tolist") else dist_sq)]
+    al = [float(a) for a in alpha]
+    nu = float(smoothing)
+    if len(ds) != len(al):
+        raise ValueError("one squared distance per weight is required")
+    if not nu > 0:
+        raise ValueError(f"smoothing must be > 0, not {smoothing}")
+    beta, objective = [], 0.0
+    for D, a in zip(ds, al):
+        d = math.sqrt(D)
+        beta.append(a / max(nu, d))
+        objective = objective + a * d
+    return beta, objective
+
+
 class ClientTable:
     """Row-major [num_clients][num_segments] device pointers + fp64 weights for one call.
 
@@ -341,6 +364,20 @@ class ClientTable:
             ws = np.asarray(self._weights, dtype=np.float64) if self._weights else np.zeros(1, np.float64)
             self._arrays = (ptrs, ws)
         return self._arrays
+
+    def set_weights(self, weights: Sequence[float]) -> None:
+        """Replace the weights in place, one per client (every present tensor of client k gets
+        ``weights[k]``; absent entries keep 0.0). The pointers are not restaged: the arrays of
+        ``arrays()`` stay where they are, so a table folded many times with new weights (the
+        geometric median's iterations) is built once."""
+        if len(weights) != self.num_clients:
+            raise ValueError("one weight per client is required")
+        T = self.num_segments
+        p, w = self.arrays()
+        n = self.num_clients * T
+        if n:
+            w[:n] = np.where(p[:n] != 0, np.repeat(np.asarray(weights, dtype=np.float64), T), 0.0)
+            self._weights = w[:n].tolist()
 
     def rows(self) -> list[list[int]]:
         T = self.num_segments
@@ -651,6 +688,48 @@ class FedAvgContext:
         _native.check(
             self._lib.fedavg_pairwise_sqdist(
                 self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, ctypes.c_void_p(out.data_ptr()), self.stream,
+            )
+        )
+        return out
+
+    def sqdist_to_point(self, table: ClientTable, in_dtype: torch.dtype,
+                        point: Sequence[torch.Tensor] | None = None) -> torch.Tensor:
+        """The length-n fp64 tensor (on the device) of squared distances of the table's clients'
+        whole updates to ``point``, ``out[i] = sum_e (x_i[e] - z[e])^2`` in fp64 with separately
+        rounded subtract, square and add (``fedavg_sqdist_to_point``; not a reference algorithm,
+        DESIGN.md §5i): the device half of the geometric median. ``point`` is one contiguous fp64
+        tensor per segment on the context's device; ``None`` is the origin (the squared norms). The
+        same bits on every run, whatever the other clients of the table. The table's weights are
+        ignored and the accumulator is not touched. Refused before any launch: an empty table, more
+        than 1024 clients, an absent entry, quantised records, a point that does not match."""
+        if table.num_clients == 0:
+            raise ValueError("distances to a point of no clients")
+        if table.num_clients > _native.POINT_MAX_CLIENTS:
+            raise NotImplementedError(
+                f"{table.num_clients} clients: distances to a point take at most {_native.POINT_MAX_CLIENTS}")
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("distances to a point read dense tensors: dequantise records first")
+        self._check_table(table, in_dtype)
+        p, _ = table.arrays()
+        absent = np.argwhere(np.asarray(p)[: table.num_clients * table.num_segments]
+                             .reshape(table.num_clients, table.num_segments) == 0)
+        if len(absent):
+            k, t = (int(x) for x in absent[0])
+            raise ValueError(f"client {k} lacks tensor {t}: distances compare whole updates")
+        zp = None
+        if point is not None:
+            if len(point) != self.layout.num_segments:
+                raise ValueError("one point tensor per segment is required")
+            for t, (z, numel) in enumerate(zip(point, self.layout.numels)):
+                if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
+                    raise ValueError(f"point tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
+            zp = (ctypes.c_void_p * len(point))(*[z.data_ptr() for z in point])
+        n = table.num_clients
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        _native.check(
+            self._lib.fedavg_sqdist_to_point(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, zp, ctypes.c_void_p(out.data_ptr()),
+                self.stream,
             )
         )
         return out

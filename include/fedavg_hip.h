@@ -128,7 +128,10 @@ int32_t fedavg_build_flags(void);
  * load: what a lane sorts per pass over its tile) of fedavg_robust_aggregate;
  * "krum_chunk" (elements per workgroup), "krum_tile" (elements staged per step), "krum_block"
  * (clients per row / column block), "krum_reg" (edge of a lane's pair block), "krum_threads",
- * "krum_max_clients" and "krum_ae_<d>" (elements of one 16-byte load) of fedavg_pairwise_sqdist.
+ * "krum_max_clients" and "krum_ae_<d>" (elements of one 16-byte load) of fedavg_pairwise_sqdist;
+ * "point_chunk" (elements per workgroup), "point_threads", "point_batch" (clients between two
+ * workgroup barriers: it does not enter the summation order), "point_max_clients" and
+ * "point_ae_<d>" (elements of one 16-byte load) of fedavg_sqdist_to_point.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -376,6 +379,49 @@ int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* client_ptrs,
 #define FEDAVG_KRUM_MAX_CLIENTS 256
 int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
                                int32_t num_clients, double* out /* [n][n], device */, void* stream);
+
+/*
+ * Squared distance of every client's whole update to one fp64 point: the device half of the
+ * geometric median's Weiszfeld iteration (RFA), and with no point the clients' squared norms. NOT
+ * an algorithm of the reference: the contract is DESIGN.md §5i, restated independently in
+ * tests/geomed_reference.py.
+ *
+ * client_ptrs[num_clients][num_segments], every entry non-NULL. point_ptrs[num_segments] (a host
+ * array): point_ptrs[t] is a device fp64 tensor of segment t's element count, 8-byte aligned;
+ * point_ptrs == NULL is the origin (out[i] = |x_i|^2); a NULL entry inside a non-NULL point_ptrs is
+ * FEDAVG_ERR_INVALID.
+ *   out[i] = sum over every element e of every segment of (x_i[e] - z[e])^2
+ * with each value converted exactly to fp64, then d = x - z, q = d * d, acc = acc + q: three
+ * separately rounded fp64 operations, NO FMA (unlike fedavg_pairwise_sqdist: these distances become
+ * continuous weights, so numpy and torch must be able to restate them bit for bit). All terms are
+ * non-negative, so each entry is within (P + 2) * 2^-53 relative of the exact value (P = the
+ * layout's element count) whatever the order. The order is fixed all the same. With C =
+ * "point_chunk", L = "point_threads" and N = "point_ae_<d>" of the client dtype:
+ *   - every segment is cut into chunks of C elements (its last chunk is shorter); a chunk's
+ *     positions past its end count as x = z = +0.0, which adds +0.0 and changes no bit;
+ *   - lane l (0 <= l < L) owns the positions (k * L + l) * N + i, k = 0 .. C / (N * L) - 1,
+ *     i = 0 .. N - 1, and adds them in ascending order into one accumulator from +0.0;
+ *   - the 64 lanes of a wave are combined by the halving tree a[l] <- a[l] + a[l + off],
+ *     l < off, off = 32, 16, 8, 4, 2, 1; the L / 64 waves are added in wave order,
+ *     ((w0 + w1) + w2) + w3;
+ *   - the chunk partials are added sequentially from +0.0 in layout order (segment by segment,
+ *     ascending offset) by a second kernel the stream orders after the first.
+ * It depends on the layout and on in_dtype (through N) alone: never on num_clients, on the client's
+ * row, on the other clients of the table, on the device or on timing (no floating-point atomics),
+ * so the same inputs give the same bits. `out` is device memory, num_clients doubles. Asynchronous
+ * on `stream`; the accumulator is not touched; nothing outside a tensor is read or written.
+ * A NaN client or point value latches FEDAVG_FLAG_INPUT_NAN (tested at the load). +inf / -inf in a
+ * client are legal (that client's entry is +inf). An infinite point element makes every finite
+ * client's entry +inf and, against the same infinity in a client, inf - inf = NaN, which latches
+ * FEDAVG_FLAG_ACC_NAN (tested on the result).
+ * fedavg_check reports the flags. in_dtype: FEDAVG_F32 / F16 / BF16 / F64 (no records, no deltas).
+ * Refused before any launch: FEDAVG_ERR_INVALID (NULL table, entry or out; bad dtype; a misaligned
+ * pointer; num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_POINT_MAX_CLIENTS 1024
+int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                               int32_t num_clients, const double* const* point_ptrs /* [num_segments] or NULL */,
+                               double* out /* [n], device */, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
