@@ -10,6 +10,7 @@ import functools
 
 from .algorithm import (
     AggregationAlgorithm,
+    ClippedFedAVGAlgorithm,
     FedAVGAlgorithm,
     GeometricMedianFedAVGAlgorithm,
     KrumFedAVGAlgorithm,
@@ -33,6 +34,7 @@ __all__ = [
     "AggregationAlgorithm",
     "AlgorithmRepository",
     "ClientTable",
+    "ClippedFedAVGAlgorithm",
     "DeltaParameterMessage",
     "FeatureMessage",
     "FedAVGAlgorithm",
@@ -95,6 +97,17 @@ def _register_builtin() -> None:
             client_cls=None,  # type: ignore[arg-type]
             server_cls=AggregationServer,
             algorithm_cls=GeometricMedianFedAVGAlgorithm,
+        )
+    # centred clipping about the previous global model: the radius has no default, so the entry
+    # is the class itself and the caller binds it (functools.partial(entry, radius=...))
+    if not AlgorithmRepository.has_algorithm("fed_centered_clipping"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_centered_clipping",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=ClippedFedAVGAlgorithm,
         )
 
 

@@ -1,9 +1,10 @@
 from .aggregation_algorithm import AggregationAlgorithm
+from .clipped_aggregation_algorithm import ClippedFedAVGAlgorithm
 from .fed_avg_algorithm import FedAVGAlgorithm
 from .geometric_median_algorithm import GeometricMedianFedAVGAlgorithm
 from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 
-__all__ = ["AggregationAlgorithm", "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "KrumFedAVGAlgorithm",
-           "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]
+__all__ = ["AggregationAlgorithm", "ClippedFedAVGAlgorithm", "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm",
+           "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]

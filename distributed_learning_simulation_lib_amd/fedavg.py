@@ -235,6 +235,33 @@ def geometric_median_step(dist_sq: Sequence[float], alpha: Sequence[float],
     return beta, objective
 
 
+def clipping_coefficients(dist_sq: Sequence[float], alpha: Sequence[float],
+                          radius: float) -> tuple[list[float], int]:
+    """The coefficients of one centred-clipping step (host arithmetic in plain Python
+    floats, shared by the GPU and the CPU path): from the clients' squared distances ``D_i`` to the
+    current centre and their weights ``alpha_i``, with ``d_i = math.sqrt(D_i)``,
+    ``c_i = 1.0 if d_i <= radius else radius / d_i`` (``D_i = +inf`` gives 0.0) and
+    ``coef_i = alpha_i * c_i``. Returns ``(coef, clipped)``: the coefficients and the number of
+    clients whose distance exceeded the radius."""
+    ds = [float(x) for x in (dist_sq.tolist() if hasattr(dist_sq, "tolist") else dist_sq)]
+    al = [float(a) for a in alpha]
+    tau = float(radius)
+    if len(ds) != len(al):
+        raise ValueError("one squared distance per weight is required")
+    if not (tau > 0 and math.isfinite(tau)):
+        raise ValueError(f"radius must be a finite number > 0, not {radius}")
+    coef, clipped = [], 0
+    for D, a in zip(ds, al):
+        d = math.sqrt(D)
+        if d <= tau:
+            c = 1.0
+        else:
+            c = tau / d
+            clipped += 1
+        coef.append(a * c)
+    return coef, clipped
+
+
 class ClientTable:
     """Row-major [num_clients][num_segments] device pointers + fp64 weights for one call.
 
@@ -733,6 +760,62 @@ class FedAvgContext:
             )
         )
         return out
+
+    def fold_about_point(self, table: ClientTable, in_dtype: torch.dtype, coefficients: Sequence[float],
+                         divisor: float, point: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                         out_dtype: torch.dtype = torch.float64) -> None:
+        """``outs[t][e] = z[e] + (sum_i c_i * (x_i[e] - z[e])) / divisor`` for every element of every
+        segment, ``z = point[t]`` (``fedavg_fold_about_point``; not a reference algorithm, DESIGN.md
+        §5j): the device half of centred clipping's step. Per element five separately rounded fp64
+        operations — subtract, multiply, add in table order (the first product starts the sum),
+        IEEE divide, add — and, for ``out_dtype=float32``, one rounding to nearest even. ``point`` is
+        one contiguous fp64 tensor per segment on the context's device, ``outs`` one contiguous
+        ``out_dtype`` tensor per segment, none of them the point's own storage. The table's weights
+        are ignored and the accumulator is not touched. Refused before any launch: an empty table,
+        more than 1024 clients, an absent entry, quantised records, a non-finite coefficient, a
+        divisor that is not finite and > 0, a point or an output that does not match, an output
+        that is its point."""
+        if table.num_clients == 0:
+            raise ValueError("the fold about a point of no clients")
+        if table.num_clients > _native.POINT_MAX_CLIENTS:
+            raise NotImplementedError(
+                f"{table.num_clients} clients: the fold about a point takes at most {_native.POINT_MAX_CLIENTS}")
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("the fold about a point reads dense tensors: dequantise records first")
+        ocode = out_code(out_dtype)
+        self._check_table(table, in_dtype)
+        n, T = table.num_clients, table.num_segments
+        p, _ = table.arrays()
+        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
+        if len(absent):
+            k, t = (int(x) for x in absent[0])
+            raise ValueError(f"client {k} lacks tensor {t}: the fold about a point takes whole updates")
+        coef = np.ascontiguousarray([float(c) for c in coefficients], dtype=np.float64)
+        if coef.shape != (n,):
+            raise ValueError(f"one coefficient per client is required: {coef.size} for {n} clients")
+        if not np.isfinite(coef).all():
+            raise ValueError("the coefficients must be finite")
+        divisor = float(divisor)
+        if not (divisor > 0 and math.isfinite(divisor)):
+            raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
+        if len(point) != T or len(outs) != T:
+            raise ValueError("one point tensor and one output tensor per segment are required")
+        for t, (z, o, numel) in enumerate(zip(point, outs, self.layout.numels)):
+            if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
+                raise ValueError(f"point tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
+            if o.dtype != out_dtype or o.device != self.device or o.numel() != numel or not o.is_contiguous():
+                raise ValueError(
+                    f"output tensor {t}: contiguous {out_dtype} of {numel} elements on {self.device} is required")
+            if o.data_ptr() == z.data_ptr():
+                raise ValueError(f"output tensor {t} is its point: the step is not in-place, ping-pong two buffers")
+        zp = (ctypes.c_void_p * T)(*[z.data_ptr() for z in point])
+        op = (ctypes.c_void_p * T)(*[o.data_ptr() for o in outs])
+        _native.check(
+            self._lib.fedavg_fold_about_point(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), coef.ctypes.data_as(_DBL), n, divisor, zp, op,
+                ocode, self.stream,
+            )
+        )
 
     def partial(
         self,

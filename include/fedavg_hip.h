@@ -131,7 +131,9 @@ int32_t fedavg_build_flags(void);
  * "krum_max_clients" and "krum_ae_<d>" (elements of one 16-byte load) of fedavg_pairwise_sqdist;
  * "point_chunk" (elements per workgroup), "point_threads", "point_batch" (clients between two
  * workgroup barriers: it does not enter the summation order), "point_max_clients" and
- * "point_ae_<d>" (elements of one 16-byte load) of fedavg_sqdist_to_point.
+ * "point_ae_<d>" (elements of one 16-byte load) of fedavg_sqdist_to_point;
+ * "clip_tile" (elements per workgroup), "clip_threads", "clip_max_clients" and "clip_ae_<d>"
+ * (elements of one 16-byte load) of fedavg_fold_about_point.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -422,6 +424,43 @@ int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* client_ptrs, 
 int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
                                int32_t num_clients, const double* const* point_ptrs /* [num_segments] or NULL */,
                                double* out /* [n], device */, void* stream);
+
+/*
+ * The fold about a point: the device half of centred clipping's step (Karimireddy, He, Jaggi,
+ * "Learning from History for Byzantine Robust Optimization"; norm bounding is its one-iteration
+ * case). NOT an algorithm of the reference: the contract is DESIGN.md §5j, restated independently in
+ * tests/clip_reference.py.
+ *
+ * client_ptrs[num_clients][num_segments], every entry non-NULL; in_dtype FEDAVG_F32 / F16 / BF16 /
+ * F64 (no records, no deltas). coefficients[num_clients] is a host array. point_ptrs[num_segments]
+ * and out_ptrs[num_segments] are host arrays of device pointers: point_ptrs[t] an fp64 tensor of
+ * segment t's element count, 8-byte aligned; out_ptrs[t] an out_dtype (FEDAVG_F32 / F64) tensor of
+ * the same count. Per element e of every segment, with z the point and c the coefficients:
+ *   d_i = x_i[e] - z[e];  p_i = c_i * d_i;  acc = p_0, then acc = acc + p_i for i = 1 .. n - 1 in
+ *   table order;  r = acc / divisor (IEEE division);  out[e] = z[e] + r
+ * with every client value converted exactly to fp64 and every operation a separately rounded fp64
+ * operation: NO FMA, and no leading 0 + (the first product starts the sum, so a sum of -0.0
+ * products stays -0.0: signed zeros come out as the five operations give them). An fp32 output is
+ * the fp64 result rounded to nearest even.
+ * The result depends on the element's own values, the coefficients in table order and the divisor
+ * alone: never on the tiling, the other elements or tensors, the device, timing or earlier calls
+ * (no atomics). Asynchronous on `stream`; the accumulator and its state are not touched; nothing
+ * outside a tensor is read or written.
+ * A NaN in a client or in the point latches FEDAVG_FLAG_INPUT_NAN (tested at the load); a NaN in acc
+ * (a NaN input, inf - inf, 0 * inf) latches FEDAVG_FLAG_ACC_NAN; a NaN in the fp64 result latches
+ * FEDAVG_FLAG_RESULT_NAN. fedavg_check reports the flags.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a NULL table, entry, point entry, out entry or
+ * coefficient array; a bad dtype; a pointer not aligned to its element; num_clients < 1 or >
+ * FEDAVG_POINT_MAX_CLIENTS; a non-finite coefficient; a divisor that is not finite and > 0;
+ * out_ptrs[t] == point_ptrs[t]: the step is not in-place, callers ping-pong two buffers),
+ * FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_fold_about_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                                const double* coefficients /* [n], host */, int32_t num_clients,
+                                double divisor,
+                                const double* const* point_ptrs /* [num_segments], device fp64 */,
+                                void* const* out_ptrs /* [num_segments], device */,
+                                int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
