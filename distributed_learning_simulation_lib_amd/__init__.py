@@ -10,6 +10,7 @@ import functools
 
 from .algorithm import (
     AggregationAlgorithm,
+    BulyanFedAVGAlgorithm,
     ClippedFedAVGAlgorithm,
     FedAVGAlgorithm,
     GeometricMedianFedAVGAlgorithm,
@@ -33,6 +34,7 @@ from .message import (
 __all__ = [
     "AggregationAlgorithm",
     "AlgorithmRepository",
+    "BulyanFedAVGAlgorithm",
     "ClientTable",
     "ClippedFedAVGAlgorithm",
     "DeltaParameterMessage",
@@ -108,6 +110,16 @@ def _register_builtin() -> None:
             client_cls=None,  # type: ignore[arg-type]
             server_cls=AggregationServer,
             algorithm_cls=ClippedFedAVGAlgorithm,
+        )
+    # Bulyan: iterated Krum, then per coordinate the mean of the values around the median
+    if not AlgorithmRepository.has_algorithm("fed_bulyan"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_bulyan",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=BulyanFedAVGAlgorithm,
         )
 
 

@@ -124,6 +124,8 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         c_int32,
         [c_void_p, _PP, c_int32, c_int32, c_int32, POINTER(c_int32), _PP, c_int32, c_void_p],
     ),
+    "fedavg_mean_around_median": (
+        c_int32, [c_void_p, _PP, c_int32, c_int32, POINTER(c_int32), _PP, c_int32, c_void_p]),
     "fedavg_pairwise_sqdist": (c_int32, [c_void_p, _PP, c_int32, c_int32, c_void_p, c_void_p]),
     "fedavg_sqdist_to_point": (c_int32, [c_void_p, _PP, c_int32, c_int32, _PP, c_void_p, c_void_p]),
     "fedavg_fold_about_point": (

@@ -1,4 +1,5 @@
 from .aggregation_algorithm import AggregationAlgorithm
+from .bulyan_aggregation_algorithm import BulyanFedAVGAlgorithm
 from .clipped_aggregation_algorithm import ClippedFedAVGAlgorithm
 from .fed_avg_algorithm import FedAVGAlgorithm
 from .geometric_median_algorithm import GeometricMedianFedAVGAlgorithm
@@ -6,5 +7,5 @@ from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 
-__all__ = ["AggregationAlgorithm", "ClippedFedAVGAlgorithm", "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm",
-           "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]
+__all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "FedAVGAlgorithm",
+           "GeometricMedianFedAVGAlgorithm", "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]

@@ -3021,7 +3021,7 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
   else if (n == "nnadq_header") v = kNnadqHeader;
   else if (n.rfind("pers_", 0) == 0) {
     if (fedavg_internal_pers_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("robust_", 0) == 0) {
+  } else if (n.rfind("robust_", 0) == 0 || n.rfind("mam_", 0) == 0) {
     if (fedavg_internal_robust_constant(name, &v) != FEDAVG_OK) v = -1;
   } else if (n.rfind("krum_", 0) == 0) {
     if (fedavg_internal_krum_constant(name, &v) != FEDAVG_OK) v = -1;

@@ -22,6 +22,8 @@
 //   * NaN: negative NaNs sort below -inf and positive ones above +inf, so s_0 and s_{n-1} tell
 //     whether any input was NaN; the result's NaN check is one compare. Both latch the context's
 //     host-coherent flag words.
+// mam_tile_kernel (fedavg_mean_around_median; tests/bulyan_reference.py) shares the
+// staging, the keys and the network and differs after the sort: see the comment above it.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -49,7 +51,7 @@ struct RSeg {      // one segment of a call
   void* out;
   int32_t first;   // index of the segment's first client pointer in the dense pointer list
   int32_t n;       // clients that sent the segment
-  int32_t k;       // values dropped at each end
+  int32_t k;       // values dropped at each end (mam_tile_kernel: beta, the values averaged)
   int32_t vec;     // every client pointer and the output are 16-byte aligned
   int64_t pad_;
 };
@@ -410,6 +412,181 @@ __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes
 }
 
 // ---------------------------------------------------------------------------------------
+// mean around the median (fedavg_mean_around_median): the mean of the beta sorted values closest
+// to the lower median. The window's start differs from lane to lane, and a register array indexed
+// by a lane's value would live in scratch, so after the network the sorted values go back into
+// the element's own staged bytes, in the input format (every value came from there, so it is
+// representable), and the window is walked in LDS: slot i of a lane is at col[(i * 4 + w) * 64],
+// congruent to the lane modulo 64 words whatever i is — no bank conflict for a lane-varying i.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+struct Sorted;  // slot i of element e in the lane's column: put a key's value there / read it as fp64
+template <>
+struct Sorted<float> {
+  __device__ __forceinline__ static void put(uint32_t* col, int i, int e, uint32_t key) {
+    col[(i * 4 + e) * kRobustLanes] = bits32(key);
+  }
+  __device__ __forceinline__ static double get(const uint32_t* col, int i, int e) {
+    return static_cast<double>(__uint_as_float(col[(i * 4 + e) * kRobustLanes]));
+  }
+};
+template <>
+struct Sorted<__half> {
+  __device__ __forceinline__ static void put(uint32_t* col, int i, int e, uint32_t key) {
+    // the key is a widened fp16 value: narrowing it is exact; the element's neighbour in the word
+    // (not sorted yet, or sorted already) keeps its 16 bits
+    const __half h = __float2half(__uint_as_float(bits32(key)));
+    reinterpret_cast<uint16_t*>(col + (i * 4 + e / 2) * kRobustLanes)[e % 2] = __half_as_ushort(h);
+  }
+  __device__ __forceinline__ static double get(const uint32_t* col, int i, int e) {
+    const uint16_t h = reinterpret_cast<const uint16_t*>(col + (i * 4 + e / 2) * kRobustLanes)[e % 2];
+    return static_cast<double>(__half2float(__ushort_as_half(h)));
+  }
+};
+template <>
+struct Sorted<bf16_t> {
+  __device__ __forceinline__ static void put(uint32_t* col, int i, int e, uint32_t key) {
+    reinterpret_cast<uint16_t*>(col + (i * 4 + e / 2) * kRobustLanes)[e % 2] = static_cast<uint16_t>(bits32(key) >> 16);
+  }
+  __device__ __forceinline__ static double get(const uint32_t* col, int i, int e) {
+    const uint32_t h = reinterpret_cast<const uint16_t*>(col + (i * 4 + e / 2) * kRobustLanes)[e % 2];
+    return static_cast<double>(__uint_as_float(h << 16));
+  }
+};
+template <>
+struct Sorted<double> {
+  __device__ __forceinline__ static void put(uint32_t* col, int i, int e, uint64_t key) {
+    const uint64_t b = bits64(key);
+    col[(i * 4 + 2 * e) * kRobustLanes] = static_cast<uint32_t>(b);
+    col[(i * 4 + 2 * e + 1) * kRobustLanes] = static_cast<uint32_t>(b >> 32);
+  }
+  __device__ __forceinline__ static double get(const uint32_t* col, int i, int e) {
+    const uint64_t lo = col[(i * 4 + 2 * e) * kRobustLanes], hi = col[(i * 4 + 2 * e + 1) * kRobustLanes];
+    return __longlong_as_double(static_cast<long long>(lo | (hi << 32)));
+  }
+};
+
+// One tile per workgroup like robust_tile_kernel, with the same staging; RSeg::k is beta, the
+// number of values averaged (1 <= beta <= n).
+template <typename T, int NPAD>
+__global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes))) void mam_tile_kernel(RArgs a) {
+  using F = Format<T>;
+  using Key = typename F::Key;
+  using L = KeyLimits<Key>;
+  using S = Sorted<T>;
+  constexpr int N = F::N;
+  constexpr int kPass = kRobustLanes * N;
+  static_assert(kRobustTile % kPass == 0, "tile geometry");
+
+  const RTile ROBUST_AS_CONST* tp = (const RTile ROBUST_AS_CONST*)(a.tiles + blockIdx.x);
+  const int32_t seg = tp->seg;
+  const int32_t count = tp->count;
+  const int64_t start = tp->start;
+  const RSeg ROBUST_AS_CONST* sp = (const RSeg ROBUST_AS_CONST*)(a.segs + seg);
+  void* const out = sp->out;
+  const int32_t n = sp->n;
+  const int32_t beta = sp->k;
+  const bool seg_vec = sp->vec != 0;
+  const void* const ROBUST_AS_CONST* ptrs = (const void* const ROBUST_AS_CONST*)(a.ptrs + sp->first);
+  const double divisor = static_cast<double>(beta);
+  const int32_t mid = (n - 1) >> 1;  // the lower median's slot
+  const int lane = static_cast<int>(threadIdx.x);
+
+  __shared__ uint32_t stage[NPAD * 4 * kRobustLanes];
+  uint32_t* const col = stage + lane;
+  __shared__ double results[8 * kRobustLanes];
+  double* const rcol = results + lane;
+  static_assert(N <= 8, "results staging");
+  constexpr int kBatch = NPAD < 16 ? NPAD : 16;
+
+  bool nan_in = false, nan_out = false;
+#pragma unroll 1
+  for (int base = 0; base < count; base += kPass) {
+    const int e0 = base + lane * N;
+    const int have = count - e0;
+    const int64_t elem = start + e0;
+    const bool vec = seg_vec && (count - base >= kPass);
+
+    static_for<NPAD / kBatch>([&](auto B) ROBUST_INLINE {
+      constexpr int b = decltype(B)::value;
+      u32x4 raw[kBatch];
+      if (vec) {
+        static_for<kBatch>([&](auto I) ROBUST_INLINE {
+          constexpr int j = b * kBatch + decltype(I)::value;
+          if (j < n) {
+            const u32x4 ROBUST_AS_GLOBAL* p =
+                (const u32x4 ROBUST_AS_GLOBAL*)((const T ROBUST_AS_GLOBAL*)ptrs[j] + elem);
+            raw[j - b * kBatch] = __builtin_nontemporal_load(p);
+          }
+        });
+      } else {
+        static_for<kBatch>([&](auto I) ROBUST_INLINE {
+          constexpr int j = b * kBatch + decltype(I)::value;
+          if (j < n) raw[j - b * kBatch] = load_guarded<T>(ptrs[j], elem, have);
+        });
+      }
+      static_for<kBatch>([&](auto I) ROBUST_INLINE {
+        constexpr int j = b * kBatch + decltype(I)::value;
+        if (j < n) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) col[(j * 4 + w) * kRobustLanes] = raw[j - b * kBatch][w];
+        }
+      });
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    asm volatile("" ::: "memory");
+
+#pragma unroll 1
+    for (int e = 0; e < N; ++e) {
+      asm volatile("" ::: "memory");
+      Key s[NPAD];
+      static_for<NPAD>([&](auto J) ROBUST_INLINE {
+        constexpr int j = decltype(J)::value;
+        s[j] = (j < n) ? F::template key<j>(col, e) : L::kMax;
+      });
+      sort_network<NPAD>(s);
+      nan_in |= s[0] < L::kNegInf;
+      // the sorted values replace the element's raw ones (slots below n only: the lane owns them)
+      static_for<NPAD>([&](auto J) ROBUST_INLINE {
+        constexpr int j = decltype(J)::value;
+        if (j == n - 1) nan_in |= s[j] > L::kPosInf;
+        if (j < n) S::put(col, j, e, s[j]);
+      });
+      asm volatile("" ::: "memory");
+      const double med = S::get(col, mid, e);
+      // the window's start: the steps t at which the value beta slots up lies closer to the median
+      // than s_t (a prefix of t: rounding is monotone). One rounded subtraction on each side; the
+      // comparison is false on NaN (inf - inf), and a tie keeps the lower value.
+      int32_t first = 0;
+#pragma unroll 4
+      for (int t = 0; t < n - beta; ++t) {
+        const double lo = S::get(col, t, e), hi = S::get(col, t + beta, e);
+        first += ((hi - med) < (med - lo)) ? 1 : 0;
+      }
+      double sum = S::get(col, first, e);  // never a leading zero: -0.0 + 0.0 would flip a sign
+#pragma unroll 4
+      for (int j = 1; j < beta; ++j) sum = sum + S::get(col, first + j, e);
+      const double r = sum / divisor;
+      rcol[e * kRobustLanes] = r;
+      nan_out |= r != r;  // elements past the tile's end are zeros here: never NaN
+    }
+    asm volatile("" ::: "memory");
+    double res[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) res[e] = rcol[e * kRobustLanes];
+
+    if (a.out_f32) {
+      store_results<float, N>(out, elem, res, vec, have);
+    } else {
+      store_results<double, N>(out, elem, res, vec, have);
+    }
+  }
+  if (__ballot(nan_in) != 0ull && lane == 0) raise_flag(a.flag, 2);
+  if (__ballot(nan_out) != 0ull && lane == 0) raise_flag(a.flag, 1);
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 struct RobustState {
@@ -478,6 +655,101 @@ void launch_npad(int npad, dim3 grid, hipStream_t s, const RArgs& a) {
   }
 }
 
+template <typename T>
+void launch_mam_npad(int npad, dim3 grid, hipStream_t s, const RArgs& a) {
+  const dim3 block(kRobustLanes);
+  switch (npad) {
+    case 2: hipLaunchKernelGGL((mam_tile_kernel<T, 2>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((mam_tile_kernel<T, 4>), grid, block, 0, s, a); break;
+    case 8: hipLaunchKernelGGL((mam_tile_kernel<T, 8>), grid, block, 0, s, a); break;
+    case 16: hipLaunchKernelGGL((mam_tile_kernel<T, 16>), grid, block, 0, s, a); break;
+    case 32: hipLaunchKernelGGL((mam_tile_kernel<T, 32>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((mam_tile_kernel<T, 64>), grid, block, 0, s, a); break;
+  }
+}
+
+// A call's tables: per segment the dense list of its non-NULL client pointers (missing clients
+// compacted away) and RSeg::k from k_of(t, n, &k), which returns FEDAVG_OK or has failed.
+template <typename KOf>
+int32_t collect_segments(const fedavg_robust_view& v, const void* const* client_ptrs, int32_t num_clients,
+                         size_t elem_bytes, void* const* out_ptrs, KOf&& k_of, std::vector<RSeg>* segs,
+                         std::vector<const void*>* list, int* nmax) {
+  const int T = v.num_segments;
+  segs->assign(T, RSeg{});
+  list->reserve(static_cast<size_t>(T) * static_cast<size_t>(num_clients < kRobustMaxClients ? num_clients : kRobustMaxClients));
+  *nmax = 0;
+  for (int t = 0; t < T; ++t) {
+    if (out_ptrs[t] == nullptr) return invalid("null output pointer");
+    RSeg& sg = (*segs)[t];
+    sg.out = out_ptrs[t];
+    sg.first = static_cast<int32_t>(list->size());
+    sg.vec = reinterpret_cast<uintptr_t>(out_ptrs[t]) % 16 == 0;
+    sg.pad_ = 0;
+    int n = 0;
+    for (int c = 0; c < num_clients; ++c) {
+      const void* p = client_ptrs[static_cast<int64_t>(c) * T + t];
+      if (p == nullptr) continue;
+      if (reinterpret_cast<uintptr_t>(p) % elem_bytes != 0) return invalid("client tensor not aligned to its element size");
+      if (reinterpret_cast<uintptr_t>(p) % 16 != 0) sg.vec = 0;
+      if (++n > kRobustMaxClients)
+        return invalid("segment " + std::to_string(t) + ": more than " + std::to_string(kRobustMaxClients) +
+                       " clients (the register-resident sort holds at most 64 values per element)");
+      list->push_back(p);
+    }
+    if (n == 0)
+      return fedavg_internal_fail(FEDAVG_ERR_STATE, ("segment " + std::to_string(t) + " has no client data").c_str());
+    int32_t k = 0;
+    const int32_t rk = k_of(t, n, &k);
+    if (rk != FEDAVG_OK) return rk;
+    sg.n = n;
+    sg.k = k;
+    *nmax = n > *nmax ? n : *nmax;
+  }
+  return FEDAVG_OK;
+}
+
+// The tables go through one of two pinned slots to the device (a slot is reused once the launch
+// that read it has finished); *a is ready for the launch, which the caller records in *slot.
+int32_t upload_tables(const fedavg_robust_view& v, const std::vector<RSeg>& segs, const std::vector<const void*>& list,
+                      int32_t out_dtype, hipStream_t s, RobustState** state, RobustState::Slot** slot, RArgs* a) {
+  ROBUST_HIP_TRY(hipSetDevice(v.device));
+  RobustState* st = nullptr;
+  const int32_t rs = ensure_state(v, &st);
+  if (rs != FEDAVG_OK) return rs;
+  const size_t seg_bytes = sizeof(RSeg) * segs.size();
+  const size_t bytes = seg_bytes + sizeof(void*) * list.size();
+  RobustState::Slot& sl = st->slots[st->next];
+  st->next ^= 1;
+  if (sl.used) ROBUST_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's tables
+  if (sl.cap < bytes) {
+    if (sl.host) ROBUST_HIP_TRY(hipHostFree(sl.host));
+    if (sl.dev) ROBUST_HIP_TRY(hipFree(sl.dev));
+    sl.host = sl.dev = nullptr;
+    sl.cap = 0;
+    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
+    ROBUST_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
+    ROBUST_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
+    sl.cap = cap;
+  }
+  std::memcpy(sl.host, segs.data(), seg_bytes);
+  std::memcpy(sl.host + seg_bytes, list.data(), sizeof(void*) * list.size());
+  ROBUST_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  a->tiles = st->d_tiles;
+  a->segs = reinterpret_cast<const RSeg*>(sl.dev);
+  a->ptrs = reinterpret_cast<const void* const*>(sl.dev + seg_bytes);
+  a->flag = v.d_flag;
+  a->out_f32 = out_dtype == FEDAVG_F32 ? 1 : 0;
+  *state = st;
+  *slot = &sl;
+  return FEDAVG_OK;
+}
+
+int npad_for(int nmax) {
+  int npad = 2;
+  while (npad < nmax) npad *= 2;
+  return npad;
+}
+
 }  // namespace
 
 int32_t fedavg_internal_robust_constant(const char* name, int64_t* out) {
@@ -489,6 +761,12 @@ int32_t fedavg_internal_robust_constant(const char* name, int64_t* out) {
   else if (n == "robust_ae_f16") *out = Format<__half>::N;
   else if (n == "robust_ae_bf16") *out = Format<bf16_t>::N;
   else if (n == "robust_ae_f64") *out = Format<double>::N;
+  else if (n == "mam_tile") *out = kRobustTile;
+  else if (n == "mam_lanes") *out = kRobustLanes;
+  else if (n == "mam_ae_f32") *out = Format<float>::N;
+  else if (n == "mam_ae_f16") *out = Format<__half>::N;
+  else if (n == "mam_ae_bf16") *out = Format<bf16_t>::N;
+  else if (n == "mam_ae_f64") *out = Format<double>::N;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
@@ -523,73 +801,29 @@ extern "C" int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* c
   if (out_ptrs == nullptr) return invalid("null out table");
   if (mode == FEDAVG_ROBUST_TRIMMED_MEAN && trim_k == nullptr) return invalid("trimmed mean needs trim_k");
 
-  const int T = v.num_segments;
   const size_t elem_bytes = in_dtype == FEDAVG_F64 ? 8 : in_dtype == FEDAVG_F32 ? 4 : 2;
-  std::vector<RSeg> segs(T);
+  std::vector<RSeg> segs;
   std::vector<const void*> list;
-  list.reserve(static_cast<size_t>(T) * static_cast<size_t>(num_clients < kRobustMaxClients ? num_clients : kRobustMaxClients));
   int nmax = 0;
-  for (int t = 0; t < T; ++t) {
-    if (out_ptrs[t] == nullptr) return invalid("null output pointer");
-    RSeg& sg = segs[t];
-    sg.out = out_ptrs[t];
-    sg.first = static_cast<int32_t>(list.size());
-    sg.vec = reinterpret_cast<uintptr_t>(out_ptrs[t]) % 16 == 0;
-    sg.pad_ = 0;
-    int n = 0;
-    for (int c = 0; c < num_clients; ++c) {
-      const void* p = client_ptrs[static_cast<int64_t>(c) * T + t];
-      if (p == nullptr) continue;
-      if (reinterpret_cast<uintptr_t>(p) % elem_bytes != 0) return invalid("client tensor not aligned to its element size");
-      if (reinterpret_cast<uintptr_t>(p) % 16 != 0) sg.vec = 0;
-      if (++n > kRobustMaxClients)
-        return invalid("segment " + std::to_string(t) + ": more than " + std::to_string(kRobustMaxClients) +
-                       " clients (the register-resident sort holds at most 64 values per element)");
-      list.push_back(p);
-    }
-    if (n == 0)
-      return fedavg_internal_fail(FEDAVG_ERR_STATE, ("segment " + std::to_string(t) + " has no client data").c_str());
-    const int k = mode == FEDAVG_ROBUST_MEDIAN ? (n - 1) / 2 : trim_k[t];
-    if (k < 0 || 2 * k >= n)
-      return invalid("segment " + std::to_string(t) + ": trim_k " + std::to_string(k) + " keeps no value of " +
-                     std::to_string(n));
-    sg.n = n;
-    sg.k = k;
-    nmax = n > nmax ? n : nmax;
-  }
-  int npad = 2;
-  while (npad < nmax) npad *= 2;
+  const int32_t rc = collect_segments(
+      v, client_ptrs, num_clients, elem_bytes, out_ptrs,
+      [&](int t, int n, int32_t* k) -> int32_t {
+        *k = mode == FEDAVG_ROBUST_MEDIAN ? (n - 1) / 2 : trim_k[t];
+        if (*k < 0 || 2 * *k >= n)
+          return invalid("segment " + std::to_string(t) + ": trim_k " + std::to_string(*k) + " keeps no value of " +
+                         std::to_string(n));
+        return FEDAVG_OK;
+      },
+      &segs, &list, &nmax);
+  if (rc != FEDAVG_OK) return rc;
+  const int npad = npad_for(nmax);
 
-  ROBUST_HIP_TRY(hipSetDevice(v.device));
-  RobustState* st = nullptr;
-  const int32_t rs = ensure_state(v, &st);
-  if (rs != FEDAVG_OK) return rs;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t seg_bytes = sizeof(RSeg) * segs.size();
-  const size_t bytes = seg_bytes + sizeof(void*) * list.size();
-  RobustState::Slot& sl = st->slots[st->next];
-  st->next ^= 1;
-  if (sl.used) ROBUST_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's tables
-  if (sl.cap < bytes) {
-    if (sl.host) ROBUST_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) ROBUST_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    ROBUST_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    ROBUST_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
-  std::memcpy(sl.host, segs.data(), seg_bytes);
-  std::memcpy(sl.host + seg_bytes, list.data(), sizeof(void*) * list.size());
-  ROBUST_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
-
+  RobustState* st = nullptr;
+  RobustState::Slot* sl = nullptr;
   RArgs a;
-  a.tiles = st->d_tiles;
-  a.segs = reinterpret_cast<const RSeg*>(sl.dev);
-  a.ptrs = reinterpret_cast<const void* const*>(sl.dev + seg_bytes);
-  a.flag = v.d_flag;
-  a.out_f32 = out_dtype == FEDAVG_F32 ? 1 : 0;
+  const int32_t ru = upload_tables(v, segs, list, out_dtype, s, &st, &sl, &a);
+  if (ru != FEDAVG_OK) return ru;
   const dim3 grid(static_cast<unsigned>(st->num_tiles));
   switch (in_dtype) {
     case FEDAVG_F32: launch_npad<float>(npad, grid, s, a); break;
@@ -598,7 +832,57 @@ extern "C" int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* c
     default: launch_npad<double>(npad, grid, s, a); break;
   }
   ROBUST_HIP_TRY(hipGetLastError());
-  ROBUST_HIP_TRY(hipEventRecord(sl.done, s));
-  sl.used = true;
+  ROBUST_HIP_TRY(hipEventRecord(sl->done, s));
+  sl->used = true;
+  return FEDAVG_OK;
+}
+
+extern "C" int32_t fedavg_mean_around_median(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                                             int32_t num_clients, const int32_t* keep, void* const* out_ptrs,
+                                             int32_t out_dtype, void* stream) {
+  fedavg_robust_view v;
+  const int32_t rv = fedavg_internal_robust_view(ctx, &v);
+  if (rv != FEDAVG_OK) return rv;
+  if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
+  if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
+    return invalid("the mean around the median reads dense fp32 / fp16 / bf16 / fp64 tensors (no records)");
+  if (out_dtype != FEDAVG_F32 && out_dtype != FEDAVG_F64) return invalid("out dtype must be FEDAVG_F32 or FEDAVG_F64");
+  if (num_clients <= 0 || client_ptrs == nullptr) return invalid("null or empty client table");
+  if (out_ptrs == nullptr) return invalid("null out table");
+  if (keep == nullptr) return invalid("the mean around the median needs keep");
+
+  const size_t elem_bytes = in_dtype == FEDAVG_F64 ? 8 : in_dtype == FEDAVG_F32 ? 4 : 2;
+  std::vector<RSeg> segs;
+  std::vector<const void*> list;
+  int nmax = 0;
+  const int32_t rc = collect_segments(
+      v, client_ptrs, num_clients, elem_bytes, out_ptrs,
+      [&](int t, int n, int32_t* k) -> int32_t {
+        *k = keep[t];
+        if (*k < 1 || *k > n)
+          return invalid("segment " + std::to_string(t) + ": keep " + std::to_string(*k) + " is not in [1, " +
+                         std::to_string(n) + "]");
+        return FEDAVG_OK;
+      },
+      &segs, &list, &nmax);
+  if (rc != FEDAVG_OK) return rc;
+  const int npad = npad_for(nmax);
+
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  RobustState* st = nullptr;
+  RobustState::Slot* sl = nullptr;
+  RArgs a;
+  const int32_t ru = upload_tables(v, segs, list, out_dtype, s, &st, &sl, &a);
+  if (ru != FEDAVG_OK) return ru;
+  const dim3 grid(static_cast<unsigned>(st->num_tiles));
+  switch (in_dtype) {
+    case FEDAVG_F32: launch_mam_npad<float>(npad, grid, s, a); break;
+    case FEDAVG_F16: launch_mam_npad<__half>(npad, grid, s, a); break;
+    case FEDAVG_BF16: launch_mam_npad<bf16_t>(npad, grid, s, a); break;
+    default: launch_mam_npad<double>(npad, grid, s, a); break;
+  }
+  ROBUST_HIP_TRY(hipGetLastError());
+  ROBUST_HIP_TRY(hipEventRecord(sl->done, s));
+  sl->used = true;
   return FEDAVG_OK;
 }

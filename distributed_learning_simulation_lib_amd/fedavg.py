@@ -212,6 +212,58 @@ def krum_select(D: Any, f: int, m: int) -> tuple[list[float], list[int]]:
     return scores, sorted(order[:m])
 
 
+def bulyan_select(D: Any, f: int) -> tuple[list[int], list[float]]:
+    """Bulyan's selection from the n x n matrix of squared distances (host arithmetic
+    in plain Python floats, shared by the GPU and the CPU path): Krum applied iteratively.
+
+    ``f`` is the assumed number of Byzantine clients (``n >= 4f + 3``); ``theta = n - 2f`` rows are
+    picked. Start from R, all rows, and repeat ``theta`` times with ``r = |R|``: if ``r == 1`` the
+    row that is left is taken with score 0.0; otherwise, with ``c = max(1, r - f - 2)``,
+    ``score_i`` (i in R) is the sum of the ``c`` smallest ``D[i][j]``, j in R without i — sorted
+    ascending, ties in ascending ``j``, added sequentially from the smallest starting at 0.0 — and
+    the row with the smallest ``(score, row)`` is picked and leaves R, so ties go to the earlier
+    arrival. The ``max(1, .)`` is this project's choice: the paper's ``r - f - 2`` neighbours run
+    out in the last picks (``r`` goes down to ``2f + 1``, where ``r - f - 2 = f - 1`` is 0 for
+    ``f = 1`` and all of R is picked for ``f = 0``), and a row is then judged by its nearest
+    neighbour. Returns ``(picked_rows, pick_scores)``: the rows in pick order and the winning
+    score of each pick."""
+    rows = [[float(x) for x in r] for r in (D.tolist() if hasattr(D, "tolist") else D)]
+    n = len(rows)
+    if any(len(r) != n for r in rows):
+        raise ValueError("the distance matrix must be square")
+    f = int(f)
+    if f < 0 or n < 4 * f + 3:
+        raise ValueError(f"Bulyan needs n >= 4f + 3 clients: n = {n}, f = {f}")
+    # every row's neighbours once, nearest first; a pick only removes entries from these lists
+    near = [sorted((d, j) for j, d in enumerate(r) if j != i) for i, r in enumerate(rows)]
+    alive = [True] * n
+    picked: list[int] = []
+    scores: list[float] = []
+    for r in range(n, 2 * f, -1):
+        best: tuple[float, int] | None = None
+        if r == 1:
+            best = (0.0, alive.index(True))
+        else:
+            c = max(1, r - f - 2)
+            for i in range(n):
+                if not alive[i]:
+                    continue
+                s, left = 0.0, c
+                for d, j in near[i]:
+                    if alive[j]:
+                        s = s + d
+                        left -= 1
+                        if left == 0:
+                            break
+                if best is None or (s, i) < best:
+                    best = (s, i)
+        assert best is not None
+        scores.append(best[0])
+        picked.append(best[1])
+        alive[best[1]] = False
+    return picked, scores
+
+
 def geometric_median_step(dist_sq: Sequence[float], alpha: Sequence[float],
                           smoothing: float) -> tuple[list[float], float]:
     """One smoothed Weiszfeld step of the geometric median (host arithmetic in plain
@@ -686,6 +738,43 @@ class FedAvgContext:
             self._lib.fedavg_robust_aggregate(
                 self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), table.num_clients,
                 _native.ROBUST_MEDIAN if mode == "median" else _native.ROBUST_TRIMMED_MEAN, ks, ot,
+                out_code(out_dtype), self.stream,
+            )
+        )
+
+    def mean_around_median(
+        self,
+        table: ClientTable,
+        in_dtype: torch.dtype,
+        keep: int | Sequence[int],
+        outs: Sequence[torch.Tensor] | OutputTable,
+        out_dtype: torch.dtype = torch.float64,
+    ) -> None:
+        """Per element the mean of the ``keep`` sorted values closest to the lower median of the
+        table's clients, one launch (``fedavg_mean_around_median``; not a reference algorithm,
+        DESIGN.md §5k): the coordinate step of Bulyan. ``keep`` is one int for every tensor or one
+        per tensor, ``1 <= keep <= n`` with n the clients that sent the tensor; ``keep == n`` is the
+        sorted-order mean, ``keep == 1`` the lower median. The table's weights are ignored and the
+        accumulator is not touched. Refused before any launch: ``keep`` out of range, a tensor sent
+        by more than 64 clients, quantised records."""
+        T = table.num_segments
+        keeps = [int(keep)] * T if isinstance(keep, (int, np.integer)) else [int(k) for k in keep]
+        if len(keeps) != T:
+            raise ValueError(f"keep has {len(keeps)} entries for {T} tensors")
+        robust_trim_counts(table, "median", 0.0)  # the refusals that need no device: 0 or > 64 senders
+        sent = (np.asarray(table.arrays()[0]).reshape(table.num_clients, T) != 0).sum(axis=0)
+        for t, (k, n) in enumerate(zip(keeps, (int(x) for x in sent))):
+            if not 1 <= k <= n:
+                raise ValueError(f"tensor {t}: keep {k} is not in [1, {n}]")
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("the mean around the median reads dense tensors: dequantise records first")
+        self._check_table(table, in_dtype)
+        p, _ = table.arrays()
+        ot = self._out_table(outs, out_dtype)
+        ks = (ctypes.c_int32 * T)(*keeps)
+        _native.check(
+            self._lib.fedavg_mean_around_median(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), table.num_clients, ks, ot,
                 out_code(out_dtype), self.stream,
             )
         )

@@ -133,7 +133,8 @@ int32_t fedavg_build_flags(void);
  * workgroup barriers: it does not enter the summation order), "point_max_clients" and
  * "point_ae_<d>" (elements of one 16-byte load) of fedavg_sqdist_to_point;
  * "clip_tile" (elements per workgroup), "clip_threads", "clip_max_clients" and "clip_ae_<d>"
- * (elements of one 16-byte load) of fedavg_fold_about_point.
+ * (elements of one 16-byte load) of fedavg_fold_about_point;
+ * "mam_tile", "mam_lanes" and "mam_ae_<d>" (as the "robust_" ones) of fedavg_mean_around_median.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -354,6 +355,37 @@ int32_t fedavg_plan_out_dtype(const fedavg_plan* plan); /* FEDAVG_F32 / FEDAVG_F
 int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
                                 int32_t num_clients, int32_t mode, const int32_t* trim_k,
                                 void* const* out_ptrs, int32_t out_dtype, void* stream);
+
+/*
+ * The mean around the median (MeaMed; Xie, Koyejo, Gupta, "Generalized Byzantine-tolerant SGD"):
+ * per element the mean of the beta values closest to the median. It is the coordinate step of
+ * Bulyan (El Mhamdi, Guerraoui, Rouault, ICML 2018). NOT an algorithm of the reference: the contract
+ * is DESIGN.md §5k, restated independently in tests/bulyan_reference.py.
+ *
+ * Tables, dtypes and compaction as fedavg_robust_aggregate: per segment t the n_t non-NULL entries
+ * of column t count (1 <= n_t <= 64), and beta = keep[t] with 1 <= keep[t] <= n_t (any beta, not
+ * only those with n_t - beta even). Per element the values, converted exactly to fp64, are sorted
+ * in the IEEE total order into s_0 <= ... <= s_{n-1}; med = s_{(n-1)/2}, the LOWER median (always
+ * an input value). The window starts at
+ *   a = #{ t in [0, n - beta) : (s_{t+beta} - med) < (med - s_t) }
+ * with one rounded fp64 subtraction on each side and the IEEE comparison (false on NaN, i.e. on
+ * inf - inf); the predicate holds on a prefix of t, so a is the first t at which it fails, and a
+ * tie keeps the lower value. The result is (s_a + s_{a+1} + ... + s_{a+beta-1}) / beta: summed in
+ * ascending order from s_a (no leading zero), every add rounded in fp64 (no FMA), IEEE division.
+ * keep[t] == n_t is the plain sorted-order mean; keep[t] == 1 is the lower median (where a -0.0 lies
+ * below a +0.0 median it ties with it and, as ties keep the lower value, -0.0 is returned).
+ * out_ptrs[num_segments]: FEDAVG_F64, or FEDAVG_F32 = that fp64 result rounded to nearest even.
+ * An element's result depends on its own n values and on beta only. One launch over the whole
+ * layout, asynchronous on `stream`; the accumulator and its state are not touched; nothing outside
+ * a tensor is read or written. A NaN input latches FEDAVG_FLAG_INPUT_NAN, a NaN result (+inf and
+ * -inf both in a window) FEDAVG_FLAG_RESULT_NAN; fedavg_check reports them.
+ * FEDAVG_ERR_INVALID (NULL tables, a bad dtype — records included —, num_clients < 1, a client
+ * pointer not aligned to its element, more than 64 clients for a segment, keep NULL or out of
+ * range), FEDAVG_ERR_STATE (a segment no client sent; an open dynamic wave) — all before any launch.
+ */
+int32_t fedavg_mean_around_median(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                                  int32_t num_clients, const int32_t* keep,
+                                  void* const* out_ptrs, int32_t out_dtype, void* stream);
 
 /*
  * Pairwise squared distances between the clients' whole updates: the device half of Krum and
