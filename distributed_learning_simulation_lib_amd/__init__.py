@@ -13,6 +13,7 @@ from .algorithm import (
     BulyanFedAVGAlgorithm,
     ClippedFedAVGAlgorithm,
     FedAVGAlgorithm,
+    FLTrustFedAVGAlgorithm,
     GeometricMedianFedAVGAlgorithm,
     KrumFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
@@ -40,6 +41,7 @@ __all__ = [
     "DeltaParameterMessage",
     "FeatureMessage",
     "FedAVGAlgorithm",
+    "FLTrustFedAVGAlgorithm",
     "FedAvgContext",
     "GeometricMedianFedAVGAlgorithm",
     "KrumFedAVGAlgorithm",
@@ -120,6 +122,17 @@ def _register_builtin() -> None:
             client_cls=None,  # type: ignore[arg-type]
             server_cls=AggregationServer,
             algorithm_cls=BulyanFedAVGAlgorithm,
+        )
+    # FLTrust: cosine trust scores against the root worker's update; the root worker has no default,
+    # so the entry is the class itself and the caller binds it (functools.partial(entry, root_worker=...))
+    if not AlgorithmRepository.has_algorithm("fed_fltrust"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_fltrust",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=FLTrustFedAVGAlgorithm,
         )
 
 

@@ -2,10 +2,12 @@ from .aggregation_algorithm import AggregationAlgorithm
 from .bulyan_aggregation_algorithm import BulyanFedAVGAlgorithm
 from .clipped_aggregation_algorithm import ClippedFedAVGAlgorithm
 from .fed_avg_algorithm import FedAVGAlgorithm
+from .fltrust_aggregation_algorithm import FLTrustFedAVGAlgorithm
 from .geometric_median_algorithm import GeometricMedianFedAVGAlgorithm
 from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 
-__all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "FedAVGAlgorithm",
-           "GeometricMedianFedAVGAlgorithm", "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm", "RobustFedAVGAlgorithm"]
+__all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "FLTrustFedAVGAlgorithm",
+           "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
+           "RobustFedAVGAlgorithm"]

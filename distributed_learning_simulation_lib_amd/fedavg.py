@@ -314,6 +314,42 @@ def clipping_coefficients(dist_sq: Sequence[float], alpha: Sequence[float],
     return coef, clipped
 
 
+def trust_coefficients(dots: Sequence[float], sqnorms: Sequence[float],
+                       root_sqnorm: float) -> tuple[list[float], list[float]]:
+    """FLTrust's trust scores and coefficients (host arithmetic in plain Python
+    floats, shared by the GPU and the CPU path): from the clients' dots ``T_i = <x_i - v, g>`` with
+    the root direction, their squared norms ``S_i = |x_i - v|^2`` and the root's own squared norm,
+    in this operation order: ``n0 = math.sqrt(root_sqnorm)``, ``ni = math.sqrt(S_i)``,
+    ``den = ni * n0``; a client whose ``S_i`` is not finite or whose ``den`` is 0 is distrusted
+    (score and coefficient 0.0); otherwise ``cos = T_i / den``, ``score = cos if cos > 0 else 0.0``
+    (the ReLU-clipped cosine; a NaN cosine scores 0.0) and ``coefficient = score * (n0 / ni)`` (the
+    score times the rescaling of the client's update to the root's norm). Returns
+    ``(scores, coefficients)``."""
+    ts = [float(x) for x in (dots.tolist() if hasattr(dots, "tolist") else dots)]
+    ss = [float(x) for x in (sqnorms.tolist() if hasattr(sqnorms, "tolist") else sqnorms)]
+    root = float(root_sqnorm)
+    if len(ts) != len(ss):
+        raise ValueError("one dot per squared norm is required")
+    n0 = math.sqrt(root)
+    scores, coef = [], []
+    for T, S in zip(ts, ss):
+        if not math.isfinite(S):
+            scores.append(0.0)
+            coef.append(0.0)
+            continue
+        ni = math.sqrt(S)
+        den = ni * n0
+        if den == 0:
+            scores.append(0.0)
+            coef.append(0.0)
+            continue
+        cos = T / den
+        score = cos if cos > 0 else 0.0
+        scores.append(score)
+        coef.append(score * (n0 / ni))
+    return scores, coef
+
+
 class ClientTable:
     """Row-major [num_clients][num_segments] device pointers + fp64 weights for one call.
 
@@ -849,6 +885,57 @@ class FedAvgContext:
             )
         )
         return out
+
+    def moments_about_point(self, table: ClientTable, in_dtype: torch.dtype,
+                            centre: Sequence[torch.Tensor] | None,
+                            direction: Sequence[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(dots, sqnorms)``: two length-n fp64 tensors (on the device) with
+        ``dots[i] = sum_e (x_i[e] - v[e]) * g[e]`` and ``sqnorms[i] = sum_e (x_i[e] - v[e])^2`` over
+        the table's clients' whole updates, from one pass over the client bytes
+        (``fedavg_moments_about_point``; not a reference algorithm): the device half
+        of FLTrust's trust scores. Per element five separately rounded fp64 operations — subtract,
+        square, multiply, two adds — in the pinned order of §5i, so ``sqnorms`` is bit for bit
+        ``sqdist_to_point(table, in_dtype, centre)``. ``centre`` (``None``: the origin) and
+        ``direction`` are one contiguous fp64 tensor per segment on the context's device. The table's
+        weights are ignored and the accumulator is not touched. Refused before any launch: an empty
+        table, more than 1024 clients, an absent entry, quantised records, a centre or a direction
+        that does not match."""
+        if table.num_clients == 0:
+            raise ValueError("moments about a point of no clients")
+        if table.num_clients > _native.POINT_MAX_CLIENTS:
+            raise NotImplementedError(
+                f"{table.num_clients} clients: moments about a point take at most {_native.POINT_MAX_CLIENTS}")
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("moments about a point read dense tensors: dequantise records first")
+        self._check_table(table, in_dtype)
+        n, T = table.num_clients, table.num_segments
+        p, _ = table.arrays()
+        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
+        if len(absent):
+            k, t = (int(x) for x in absent[0])
+            raise ValueError(f"client {k} lacks tensor {t}: moments compare whole updates")
+        if direction is None:
+            raise ValueError("the direction is required")
+        tables = []
+        for what, tensors in (("centre", centre), ("direction", direction)):
+            if tensors is None:
+                tables.append(None)
+                continue
+            if len(tensors) != T:
+                raise ValueError(f"one {what} tensor per segment is required")
+            for t, (z, numel) in enumerate(zip(tensors, self.layout.numels)):
+                if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
+                    raise ValueError(
+                        f"{what} tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
+            tables.append((ctypes.c_void_p * T)(*[z.data_ptr() for z in tensors]))
+        out = torch.empty((2, n), dtype=torch.float64, device=self.device)
+        _native.check(
+            self._lib.fedavg_moments_about_point(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, tables[0], tables[1],
+                ctypes.c_void_p(out.data_ptr()), self.stream,
+            )
+        )
+        return out[0], out[1]
 
     def fold_about_point(self, table: ClientTable, in_dtype: torch.dtype, coefficients: Sequence[float],
                          divisor: float, point: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],

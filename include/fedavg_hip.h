@@ -134,7 +134,11 @@ int32_t fedavg_build_flags(void);
  * "point_ae_<d>" (elements of one 16-byte load) of fedavg_sqdist_to_point;
  * "clip_tile" (elements per workgroup), "clip_threads", "clip_max_clients" and "clip_ae_<d>"
  * (elements of one 16-byte load) of fedavg_fold_about_point;
- * "mam_tile", "mam_lanes" and "mam_ae_<d>" (as the "robust_" ones) of fedavg_mean_around_median.
+ * "mam_tile", "mam_lanes" and "mam_ae_<d>" (as the "robust_" ones) of fedavg_mean_around_median;
+ * "trust_chunk" (elements per workgroup: equal to "point_chunk"), "trust_threads", "trust_batch"
+ * (clients between two workgroup barriers: it does not enter the summation order),
+ * "trust_max_clients" and "trust_ae_<d>" (elements of one 16-byte load) of
+ * fedavg_moments_about_point.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -493,6 +497,48 @@ int32_t fedavg_fold_about_point(fedavg_ctx* ctx, const void* const* client_ptrs,
                                 const double* const* point_ptrs /* [num_segments], device fp64 */,
                                 void* const* out_ptrs /* [num_segments], device */,
                                 int32_t out_dtype, void* stream);
+
+/*
+ * The two moments of every client's whole update about one fp64 point: the device half of FLTrust's
+ * trust scores (Cao, Fang, Liu, Gong, "FLTrust: Byzantine-robust Federated Learning via Trust
+ * Bootstrapping", NDSS 2021). NOT an algorithm of the reference: the contract is DESIGN.md §5l,
+ * restated independently in tests/trust_reference.py.
+ *
+ * client_ptrs[num_clients][num_segments], every entry non-NULL; in_dtype FEDAVG_F32 / F16 / BF16 /
+ * F64 (no records, no deltas). centre_ptrs[num_segments] and direction_ptrs[num_segments] are host
+ * arrays of device pointers to fp64 tensors of the segments' element counts, 8-byte aligned;
+ * centre_ptrs == NULL is the origin, direction_ptrs is required. With v the centre and g the
+ * direction, for client i and every element e of every segment:
+ *   d = x_i[e] - v[e];  q = d * d;  p = d * g[e];  S_i = S_i + q;  T_i = T_i + p
+ * with every client value converted exactly to fp64 and every operation a separately rounded fp64
+ * operation, NO FMA. out[i] = T_i (the dots) and out[num_clients + i] = S_i (the squared norms);
+ * `out` is device memory, 2 * num_clients doubles.
+ * Both sums follow the summation order of fedavg_sqdist_to_point word for word, with C =
+ * "trust_chunk" (== "point_chunk"), L = "trust_threads" and N = "trust_ae_<d>": chunks of C elements
+ * per segment, padded with x = v = g = +0.0 (an accumulator that starts at +0.0 is never -0.0, so
+ * the padding's +0.0 changes no bit of either sum); lane l owns the positions (k * L + l) * N + i in
+ * ascending order, one accumulator per sum from +0.0; the halving tree over the 64 lanes of a wave;
+ * the waves in wave order; the chunk partials sequentially from +0.0 in layout order, in a second
+ * kernel the stream orders after the first. So out[num_clients + i] is bit for bit what
+ * fedavg_sqdist_to_point returns for the same table and point, and a client's two entries depend on
+ * the layout, in_dtype and its own values alone: never on num_clients, its row, the other clients,
+ * the device or timing (no floating-point atomics). A dot's terms have both signs: it is within
+ * (P + 2) * 2^-53 * sum_e |(x - v) * g| of the exact value (P = the layout's element count).
+ * Asynchronous on `stream`; the accumulator is not touched; nothing outside a tensor is read or
+ * written.
+ * A NaN in a client, the centre or the direction latches FEDAVG_FLAG_INPUT_NAN (tested at the load);
+ * a NaN in any output (inf - inf, 0 * inf, +inf + -inf in a dot) latches FEDAVG_FLAG_ACC_NAN (tested
+ * on the result). fedavg_check reports the flags.
+ * Refused before any launch, with the flags and `out` untouched: FEDAVG_ERR_INVALID (a NULL client
+ * table, direction table or out; a NULL client, centre or direction entry; a bad dtype; a client
+ * pointer not aligned to its element size; a centre, direction or out pointer not aligned to 8
+ * bytes; num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                                   int32_t num_clients,
+                                   const double* const* centre_ptrs /* [num_segments] fp64, or NULL: the origin */,
+                                   const double* const* direction_ptrs /* [num_segments] fp64, required */,
+                                   double* out /* [2][n], device: dots, then squared norms */, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
