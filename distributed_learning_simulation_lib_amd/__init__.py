@@ -18,6 +18,7 @@ from .algorithm import (
     KrumFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
+    ServerOptFedAVGAlgorithm,
 )
 from .algorithm_repository import AlgorithmRepository
 from .fedavg import ClientTable, FedAvgContext, ModelLayout, NaNAggregationError
@@ -54,6 +55,7 @@ __all__ = [
     "ParameterMessageBase",
     "PersonalizedFedAVGAlgorithm",
     "RobustFedAVGAlgorithm",
+    "ServerOptFedAVGAlgorithm",
     "get_message_size",
 ]
 
@@ -134,6 +136,20 @@ def _register_builtin() -> None:
             server_cls=AggregationServer,
             algorithm_cls=FLTrustFedAVGAlgorithm,
         )
+    # the FedOpt server optimisers (Reddi et al.): the learning rate of the adaptive ones has no
+    # default, so the caller binds it (functools.partial(entry, learning_rate=...)); "fed_avgm" runs
+    # as it is, at learning rate 1.0
+    for name, optimizer in (("fed_avgm", "avgm"), ("fed_adagrad", "adagrad"), ("fed_yogi", "yogi"),
+                            ("fed_adam", "adam")):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=functools.partial(ServerOptFedAVGAlgorithm, optimizer=optimizer),
+            )
 
 
 _register_builtin()

@@ -7,7 +7,8 @@ from .geometric_median_algorithm import GeometricMedianFedAVGAlgorithm
 from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
+from .server_opt_algorithm import ServerOptFedAVGAlgorithm
 
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "FLTrustFedAVGAlgorithm",
            "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
-           "RobustFedAVGAlgorithm"]
+           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm"]

@@ -350,6 +350,71 @@ def trust_coefficients(dots: Sequence[float], sqnorms: Sequence[float],
     return scores, coef
 
 
+SERVER_OPT_MODES = ("avgm", "adagrad", "yogi", "adam")  # FEDAVG_OPT_AVGM / ADAGRAD / YOGI / ADAM in this order
+
+
+def check_server_opt(mode: str, lr: float, beta1: float, beta2: float,
+                     tau: float) -> tuple[int, float, float, float, float, float, float]:
+    """The hyper-parameters of a server optimiser step, validated as the C call
+    validates them: ``mode`` one of ``SERVER_OPT_MODES``; ``lr`` finite and > 0; ``beta1`` and
+    ``beta2`` in [0, 1); ``tau`` finite and > 0 in the adaptive modes (``"avgm"`` ignores it).
+    Returns ``(code, lr, beta1, 1 - beta1, beta2, 1 - beta2, tau)`` as Python floats: ``1 - beta`` is
+    computed here once, so the kernel, the CPU path and a restatement use the same doubles."""
+    if mode not in SERVER_OPT_MODES:
+        raise ValueError(f"mode must be one of {SERVER_OPT_MODES}, not {mode!r}")
+    lr, beta1, beta2, tau = float(lr), float(beta1), float(beta2), float(tau)
+    if not (lr > 0 and math.isfinite(lr)):
+        raise ValueError(f"the learning rate must be a finite number > 0, not {lr}")
+    for name, b in (("beta1", beta1), ("beta2", beta2)):
+        if not 0 <= b < 1:
+            raise ValueError(f"{name} must lie in [0, 1), not {b}")
+    if mode != "avgm" and not (tau > 0 and math.isfinite(tau)):
+        raise ValueError(f"tau must be a finite number > 0, not {tau}")
+    return SERVER_OPT_MODES.index(mode), lr, beta1, 1.0 - beta1, beta2, 1.0 - beta2, tau
+
+
+def _sqrt_rn(t: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded float64 square root of a CPU tensor. ``torch.sqrt``'s CPU kernel goes
+    through a vector maths library whose results are off by one ulp for some inputs (measured: 670
+    of 100 000 uniform values against ``numpy.sqrt``), so the root — and it alone — is taken by numpy,
+    which uses the processor's IEEE instruction."""
+    with np.errstate(invalid="ignore"):
+        r = np.sqrt(t.detach().contiguous().numpy().reshape(-1))
+    return torch.from_numpy(r).reshape(t.shape)
+
+
+def server_opt_update(mode: str, delta: torch.Tensor, m: torch.Tensor, v: torch.Tensor | None, lr: float,
+                      beta1: float, one_minus_beta1: float, beta2: float, one_minus_beta2: float,
+                      tau: float) -> tuple[torch.Tensor, torch.Tensor | None, torch.Tensor]:
+    """The optimiser lines of ``fedavg_server_opt_step`` in torch, one float64 operation per line
+    (DESIGN.md §5m): from the pseudo-gradient ``delta`` and the moments ``m``, ``v`` returns
+    ``(m', v', u)``; the new model is ``z + u``. ``v`` and ``v'`` are ``None`` for ``"avgm"``. CPU
+    tensors only (the square root is ``_sqrt_rn``)."""
+    a = beta1 * m
+    if mode == "avgm":
+        m_new = a + delta
+        return m_new, None, lr * m_new
+    b = one_minus_beta1 * delta
+    m_new = a + b
+    q = delta * delta
+    if mode == "adagrad":
+        v_new = v + q
+    elif mode == "adam":
+        e = beta2 * v
+        f = one_minus_beta2 * q
+        v_new = e + f
+    else:  # yogi
+        g = v - q
+        s = (g > 0).to(torch.float64) - (g < 0).to(torch.float64)  # +1.0, -1.0, else (NaN included) +0.0
+        f = one_minus_beta2 * q
+        h = f * s
+        v_new = v - h
+    r = _sqrt_rn(v_new)
+    den = r + tau
+    num = lr * m_new
+    return m_new, v_new, num / den
+
+
 class ClientTable:
     """Row-major [num_clients][num_segments] device pointers + fp64 weights for one call.
 
@@ -990,6 +1055,79 @@ class FedAvgContext:
             self._lib.fedavg_fold_about_point(
                 self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), coef.ctypes.data_as(_DBL), n, divisor, zp, op,
                 ocode, self.stream,
+            )
+        )
+
+    def server_opt_step(self, table: ClientTable, in_dtype: torch.dtype, coefficients: Sequence[float],
+                        divisor: float, point: Sequence[torch.Tensor], m_in: Sequence[torch.Tensor],
+                        v_in: Sequence[torch.Tensor] | None, m_out: Sequence[torch.Tensor],
+                        v_out: Sequence[torch.Tensor] | None, outs: Sequence[torch.Tensor],
+                        out_dtype: torch.dtype = torch.float64, *, mode: str, lr: float, beta1: float,
+                        beta2: float, tau: float) -> None:
+        """One server optimiser step (``fedavg_server_opt_step``; not a reference algorithm, DESIGN.md
+        §5m): the pseudo-gradient ``delta = (sum_i c_i * (x_i - z)) / divisor`` of
+        ``fold_about_point``, the moments ``m_out``, ``v_out`` from ``m_in``, ``v_in`` by ``mode``
+        (``"avgm"``, ``"adagrad"``, ``"yogi"``, ``"adam"``: ``server_opt_update`` states the lines)
+        and ``outs = z + u``, in one pass over the client bytes. Every line is one separately rounded
+        fp64 operation, the square root is correctly rounded, ``1 - beta`` is computed once here.
+        ``point``, ``m_in``, ``v_in``, ``m_out``, ``v_out`` are one contiguous fp64 tensor per segment
+        on the context's device (``v_in`` / ``v_out`` are ignored for ``"avgm"`` and may be ``None``),
+        ``outs`` one contiguous ``out_dtype`` tensor per segment. Not in-place: ``outs`` is not the
+        point and no ``*_out`` is its ``*_in``; the caller swaps its buffers once ``flags()`` came back
+        clean. Refused before any launch: what ``fold_about_point`` refuses, the hyper-parameters
+        ``check_server_opt`` refuses, moments that do not match or alias."""
+        if table.num_clients == 0:
+            raise ValueError("the server optimiser step of no clients")
+        if table.num_clients > _native.POINT_MAX_CLIENTS:
+            raise NotImplementedError(
+                f"{table.num_clients} clients: the server optimiser step takes at most {_native.POINT_MAX_CLIENTS}")
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError("the server optimiser step reads dense tensors: dequantise records first")
+        ocode = out_code(out_dtype)
+        code, lr, beta1, omb1, beta2, omb2, tau = check_server_opt(mode, lr, beta1, beta2, tau)
+        self._check_table(table, in_dtype)
+        n, T = table.num_clients, table.num_segments
+        p, _ = table.arrays()
+        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
+        if len(absent):
+            k, t = (int(x) for x in absent[0])
+            raise ValueError(f"client {k} lacks tensor {t}: the server optimiser step takes whole updates")
+        coef = np.ascontiguousarray([float(c) for c in coefficients], dtype=np.float64)
+        if coef.shape != (n,):
+            raise ValueError(f"one coefficient per client is required: {coef.size} for {n} clients")
+        if not np.isfinite(coef).all():
+            raise ValueError("the coefficients must be finite")
+        divisor = float(divisor)
+        if not (divisor > 0 and math.isfinite(divisor)):
+            raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
+        adaptive = code != _native.OPT_AVGM
+        groups = [("point", point), ("first-moment input", m_in), ("first-moment output", m_out)]
+        if adaptive:
+            if v_in is None or v_out is None:
+                raise ValueError(f"mode {mode!r} needs second-moment tensors")
+            groups += [("second-moment input", v_in), ("second-moment output", v_out)]
+        if len(outs) != T or any(len(g) != T for _, g in groups):
+            raise ValueError("one point, moment and output tensor per segment are required")
+        for what, tensors in groups:
+            for t, (z, numel) in enumerate(zip(tensors, self.layout.numels)):
+                if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
+                    raise ValueError(
+                        f"{what} tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
+        for t, (o, numel) in enumerate(zip(outs, self.layout.numels)):
+            if o.dtype != out_dtype or o.device != self.device or o.numel() != numel or not o.is_contiguous():
+                raise ValueError(
+                    f"output tensor {t}: contiguous {out_dtype} of {numel} elements on {self.device} is required")
+            if o.data_ptr() == point[t].data_ptr():
+                raise ValueError(f"output tensor {t} is its point: the step is not in-place, ping-pong two buffers")
+            if m_out[t].data_ptr() == m_in[t].data_ptr() or (adaptive and v_out[t].data_ptr() == v_in[t].data_ptr()):
+                raise ValueError(f"moment tensor {t}: the step is not in-place, ping-pong two buffers")
+        arrays = [(ctypes.c_void_p * T)(*[z.data_ptr() for z in g]) if g is not None else None
+                  for g in (point, m_in, v_in if adaptive else None, m_out, v_out if adaptive else None, outs)]
+        _native.check(
+            self._lib.fedavg_server_opt_step(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), coef.ctypes.data_as(_DBL), n, divisor,
+                arrays[0], arrays[1], arrays[2], arrays[3], arrays[4], code, lr, beta1, omb1, beta2, omb2, tau,
+                arrays[5], ocode, self.stream,
             )
         )
 

@@ -138,7 +138,9 @@ int32_t fedavg_build_flags(void);
  * "trust_chunk" (elements per workgroup: equal to "point_chunk"), "trust_threads", "trust_batch"
  * (clients between two workgroup barriers: it does not enter the summation order),
  * "trust_max_clients" and "trust_ae_<d>" (elements of one 16-byte load) of
- * fedavg_moments_about_point.
+ * fedavg_moments_about_point;
+ * "opt_tile" (elements per workgroup), "opt_threads", "opt_max_clients" and "opt_ae_<d>" (elements
+ * of one 16-byte load) of fedavg_server_opt_step.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -539,6 +541,64 @@ int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const* client_pt
                                    const double* const* centre_ptrs /* [num_segments] fp64, or NULL: the origin */,
                                    const double* const* direction_ptrs /* [num_segments] fp64, required */,
                                    double* out /* [2][n], device: dots, then squared norms */, void* stream);
+
+/*
+ * The server optimiser step: the fold about a point with the FedOpt epilogue fused onto it (Reddi et
+ * al., "Adaptive Federated Optimization", ICLR 2021: FedAvgM, FedAdagrad, FedYogi, FedAdam). NOT an
+ * algorithm of the reference: the contract is DESIGN.md §5m, restated independently in
+ * tests/opt_reference.py.
+ *
+ * client_ptrs, in_dtype, coefficients, num_clients, divisor, point_ptrs, out_ptrs and out_dtype are
+ * those of fedavg_fold_about_point. m_in, v_in, m_out and v_out are host arrays [num_segments] of
+ * device pointers to fp64 tensors of the segments' element counts, 8-byte aligned: the moments
+ * before the step and where the moments after it are written. FEDAVG_OPT_AVGM keeps no second
+ * moment: v_in and v_out are not read and may be NULL. one_minus_beta1 and one_minus_beta2 are
+ * passed in (the caller computes 1 - beta once) so a restatement uses the very same doubles.
+ * Per element e of every segment, with z the point, c the coefficients, m and v the moments:
+ *   d_i = x_i[e] - z[e];  p_i = c_i * d_i;  acc = p_0, then acc = acc + p_i for i = 1 .. n - 1 in
+ *   table order;  delta = acc / divisor       (so far bit for bit the r of fedavg_fold_about_point)
+ *   AVGM:     a = beta1 * m;  m' = a + delta;                               u = lr * m'
+ *   others:   a = beta1 * m;  b = one_minus_beta1 * delta;  m' = a + b;  q = delta * delta
+ *     ADAGRAD:  v' = v + q
+ *     ADAM:     e = beta2 * v;  f = one_minus_beta2 * q;  v' = e + f
+ *     YOGI:     g = v - q;  s = +1.0 if g > 0, -1.0 if g < 0, else +0.0;
+ *               f = one_minus_beta2 * q;  h = f * s;  v' = v - h
+ *     r = sqrt(v');  den = r + tau;  num = lr * m';  u = num / den
+ *   out[e] = z[e] + u;  m_out[e] = m';  v_out[e] = v'
+ * with every client value converted exactly to fp64 and every line one separately rounded IEEE fp64
+ * operation: NO FMA, no reciprocal, IEEE division, a correctly rounded square root, no bias
+ * correction (the paper has none). An fp32 output is the fp64 result rounded to nearest even.
+ * The results depend on the element's own values, the coefficients in table order, the divisor and
+ * the hyper-parameters alone: never on the tiling, the other elements or tensors, the device,
+ * timing or earlier calls (no atomics, no workspace, one kernel). Asynchronous on `stream`; the
+ * accumulator and its state are not touched; nothing outside a tensor is read or written.
+ * A NaN in a client, the point, m or v latches FEDAVG_FLAG_INPUT_NAN (tested at the load); a NaN in
+ * acc latches FEDAVG_FLAG_ACC_NAN; a NaN in out, m' or v' latches FEDAVG_FLAG_RESULT_NAN. In the
+ * adaptive modes an infinite client value makes u = inf / inf: it latches FEDAVG_FLAG_RESULT_NAN,
+ * an error and not a drop. (FEDAVG_OPT_AVGM has no quotient: there it gives an infinite out and m'
+ * and no flag, as the weighted mean itself would.) The step is not in-place: a caller ping-pongs
+ * two buffers per moment and swaps them once fedavg_check came back clean, so a failed round leaves
+ * its state intact.
+ * Refused before any launch: FEDAVG_ERR_INVALID (everything fedavg_fold_about_point refuses; an
+ * unknown mode; lr not finite or not > 0; beta1 or beta2 outside [0, 1); in the adaptive modes tau
+ * not finite or not > 0; a NULL moment table or entry that the mode needs, or one not aligned to 8
+ * bytes; for any segment out_ptrs[t] == point_ptrs[t], m_out[t] == m_in[t] or
+ * v_out[t] == v_in[t]), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_OPT_AVGM 0
+#define FEDAVG_OPT_ADAGRAD 1
+#define FEDAVG_OPT_YOGI 2
+#define FEDAVG_OPT_ADAM 3
+int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                               const double* coefficients /* [n], host */, int32_t num_clients,
+                               double divisor,
+                               const double* const* point_ptrs /* [num_segments], device fp64 */,
+                               const double* const* m_in, const double* const* v_in /* NULL for AVGM */,
+                               double* const* m_out, double* const* v_out /* NULL for AVGM */,
+                               int32_t mode, double lr, double beta1, double one_minus_beta1,
+                               double beta2, double one_minus_beta2, double tau,
+                               void* const* out_ptrs /* [num_segments], device */,
+                               int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
