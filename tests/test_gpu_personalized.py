@@ -161,7 +161,7 @@ def test_int_weights_ring_with_uneven_wave_counts(hip_device, receivers, ring, m
 
 
 def test_two_receiver_groups_carry_the_central_chain(hip_device):
-    # 130 receivers > 120 per launch: the second launch continues the centralized chain
+    # 130 receivers > 128 per launch (kGroup): the second launch continues the centralized chain
     clients, ww = _random_round(130, range(130), {"a": (257,), "b": (3, 5)}, 102)
     _assert_same(_hip(clients, ww, hip_device), _oracle(clients, ww))
 
