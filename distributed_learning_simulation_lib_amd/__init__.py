@@ -19,6 +19,7 @@ from .algorithm import (
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
     ServerOptFedAVGAlgorithm,
+    SparseFedAVGAlgorithm,
 )
 from .algorithm_repository import AlgorithmRepository
 from .fedavg import ClientTable, FedAvgContext, ModelLayout, NaNAggregationError
@@ -32,6 +33,7 @@ from .message import (
     ParameterMessageBase,
     get_message_size,
 )
+from .sparse import SparseDelta, topk_sparsify
 
 __all__ = [
     "AggregationAlgorithm",
@@ -56,7 +58,10 @@ __all__ = [
     "PersonalizedFedAVGAlgorithm",
     "RobustFedAVGAlgorithm",
     "ServerOptFedAVGAlgorithm",
+    "SparseDelta",
+    "SparseFedAVGAlgorithm",
     "get_message_size",
+    "topk_sparsify",
 ]
 
 
@@ -150,6 +155,16 @@ def _register_builtin() -> None:
                 server_cls=AggregationServer,
                 algorithm_cls=functools.partial(ServerOptFedAVGAlgorithm, optimizer=optimizer),
             )
+    # FedAvg over sparsified parameter diffs (top-k clients with error feedback), folded as they are
+    if not AlgorithmRepository.has_algorithm("fed_avg_sparse"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_avg_sparse",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=SparseFedAVGAlgorithm,
+        )
 
 
 _register_builtin()

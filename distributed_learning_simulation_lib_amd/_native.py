@@ -40,7 +40,7 @@ ROBUST_TRIMMED_MEAN, ROBUST_MEDIAN = 0, 1  # FEDAVG_ROBUST_*: fedavg_robust_aggr
 ROBUST_MAX_CLIENTS = 64
 KRUM_MAX_CLIENTS = 256  # FEDAVG_KRUM_MAX_CLIENTS: fedavg_pairwise_sqdist
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
-# fedavg_moments_about_point, fedavg_server_opt_step
+# fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta
 OPT_AVGM, OPT_ADAGRAD, OPT_YOGI, OPT_ADAM = 0, 1, 2, 3  # FEDAVG_OPT_*: fedavg_server_opt_step modes
 ABI_VERSION = 1
 ACC_ALIGN = 32  # FEDAVG_ACC_ALIGN: accumulator segments start at multiples of 32 elements
@@ -136,6 +136,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_server_opt_step": (
         c_int32, [c_void_p, _PP, c_int32, _PD, c_int32, c_double, _PP, _PP, _PP, _PP, _PP, c_int32, c_double,
                   c_double, c_double, c_double, c_double, c_double, _PP, c_int32, c_void_p]),
+    "fedavg_sparse_aggregate_delta": (
+        c_int32, [c_void_p, _PP, _PP, POINTER(c_int64), c_int32, _PD, c_int32, c_double, _PP, _PP, c_int32, c_void_p]),
+    "fedavg_sparse_index_errors": (c_int32, [c_void_p, c_void_p, POINTER(c_int32)]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

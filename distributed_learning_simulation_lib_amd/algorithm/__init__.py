@@ -8,7 +8,8 @@ from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 from .server_opt_algorithm import ServerOptFedAVGAlgorithm
+from .sparse_fed_avg_algorithm import SparseFedAVGAlgorithm
 
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "FLTrustFedAVGAlgorithm",
            "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "KrumFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
-           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm"]
+           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SparseFedAVGAlgorithm"]

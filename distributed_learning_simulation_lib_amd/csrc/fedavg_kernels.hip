@@ -44,6 +44,7 @@
 #include "krum_internal.h"
 #include "point_internal.h"
 #include "clip_internal.h"
+#include "sparse_internal.h"
 #include "trust_internal.h"
 #include "opt_internal.h"
 
@@ -2257,6 +2258,9 @@ struct fedavg_ctx {
   void* trust = nullptr;
   // per-context state of the server optimiser step (opt_kernels.hip: tile table, table staging)
   void* opt = nullptr;
+  // per-context state of the sparse delta fold (sparse_kernels.hip: tile table, table staging,
+  // the index-violation word)
+  void* sparse = nullptr;
   // the dynamic wave (fedavg_dyn_*): its host-coherent control block and row table, the device
   // mirror words, a private stream (the caller's stream stays free for the work producing the
   // arrivals) and the per-segment totals of the published rows
@@ -3039,6 +3043,8 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
     if (fedavg_internal_trust_constant(name, &v) != FEDAVG_OK) v = -1;
   } else if (n.rfind("opt_", 0) == 0) {
     if (fedavg_internal_opt_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (n.rfind("sparse_", 0) == 0) {
+    if (fedavg_internal_sparse_constant(name, &v) != FEDAVG_OK) v = -1;
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);
@@ -3273,6 +3279,7 @@ int32_t fedavg_ctx_destroy(fedavg_ctx* c) {
   if (c->clip) fedavg_internal_clip_release(c->device, c->clip);
   if (c->trust) fedavg_internal_trust_release(c->device, c->trust);
   if (c->opt) fedavg_internal_opt_release(c->device, c->opt);
+  if (c->sparse) fedavg_internal_sparse_release(c->device, c->sparse);
   delete c;
   return FEDAVG_OK;
 }
@@ -3516,6 +3523,12 @@ int32_t fedavg_internal_trust_slot(fedavg_ctx* c, void*** slot) {
 int32_t fedavg_internal_opt_slot(fedavg_ctx* c, void*** slot) {
   FEDAVG_RET(check_ctx(c));
   *slot = &c->opt;
+  return FEDAVG_OK;
+}
+
+int32_t fedavg_internal_sparse_slot(fedavg_ctx* c, void*** slot) {
+  FEDAVG_RET(check_ctx(c));
+  *slot = &c->sparse;
   return FEDAVG_OK;
 }
 

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .sparse import SparseDelta
 
 DTYPE_CODES: dict[torch.dtype, int] = {
     torch.float32: _native.F32,
@@ -599,6 +600,50 @@ class OutputTable:
         return self
 
 
+SPARSE_INDEX_MESSAGE = ("a sparse delta's indices are not strictly increasing inside [0, numel): "
+                        "duplicate, descending, negative or past the tensor's end")
+
+
+class SparseTable:
+    """Validated rows of sparse deltas as the C-ABI arrays of ``fedavg_sparse_aggregate_delta``:
+    ``rows[i][t]`` is client ``i``'s ``SparseDelta`` of segment ``t`` of ``layout`` on ``device``, all
+    of one value dtype (built once, reusable across calls; it keeps the tensors alive)."""
+
+    def __init__(self, rows: Sequence[Sequence[SparseDelta]], layout: ModelLayout, device: torch.device) -> None:
+        n, T = len(rows), layout.num_segments
+        if n == 0:
+            raise ValueError("the sparse fold of no clients")
+        if n > _native.POINT_MAX_CLIENTS:
+            raise NotImplementedError(f"{n} clients: the sparse fold takes at most {_native.POINT_MAX_CLIENTS}")
+        dtypes = set()
+        self.iptr = np.zeros(n * T, dtype=np.uint64)
+        self.vptr = np.zeros(n * T, dtype=np.uint64)
+        self.nnz = np.zeros(n * T, dtype=np.int64)
+        for i, row in enumerate(rows):
+            if len(row) != T:
+                raise ValueError(f"client {i}: one sparse delta per segment is required")
+            for t, (d, numel) in enumerate(zip(row, layout.numels)):
+                if not isinstance(d, SparseDelta):
+                    raise TypeError(f"client {i}, tensor {t}: a SparseDelta is required, not {type(d).__name__}")
+                if d.numel != numel or d.indices.device != device or d.values.device != device \
+                        or not d.indices.is_contiguous() or not d.values.is_contiguous():
+                    raise ValueError(f"client {i}, tensor {t}: a contiguous sparse delta of {numel} elements on "
+                                     f"{device} is required")
+                dtypes.add(d.values.dtype)
+                k = i * T + t
+                self.nnz[k] = d.nnz
+                if d.nnz:
+                    self.iptr[k] = d.indices.data_ptr()
+                    self.vptr[k] = d.values.data_ptr()
+        if len(dtypes) != 1:
+            raise ValueError(f"the sparse deltas of one call share one value dtype, not {sorted(map(str, dtypes))}")
+        self.dtype = dtypes.pop()
+        self.num_clients = n
+        self.layout = layout
+        self.device = device
+        self._keep = [list(row) for row in rows]
+
+
 class FedAvgContext:
     """One native FedAvg context: layout + device + fp64 accumulator."""
 
@@ -1057,6 +1102,69 @@ class FedAvgContext:
                 ocode, self.stream,
             )
         )
+
+    def sparse_aggregate_delta(self, rows: Sequence[Sequence[SparseDelta]] | SparseTable, weights: Sequence[float],
+                               divisor: float,
+                               base: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                               out_dtype: torch.dtype = torch.float64, check_indices: bool = True) -> None:
+        """FedAvg of sparse deltas against ``base`` in one launch (``fedavg_sparse_aggregate_delta``,
+        DESIGN.md §5n): ``outs[t][e] = (sum_i (base[t][e] + d_i[e]) * w_i) / divisor`` with ``d_i[e]``
+        the value client ``i`` stores for ``e`` or ``+0.0`` — bit for bit the reference's ``restore()``
+        + ``FedAVGAlgorithm`` on the densified deltas, and ``aggregate_delta`` on them. ``rows[i][t]``
+        is client ``i``'s ``SparseDelta`` of segment ``t`` on the context's device, all of one value
+        dtype (or a ``SparseTable`` built from such rows once, for a table that is folded many times);
+        ``base`` one contiguous fp64 tensor per segment, ``outs`` one contiguous ``out_dtype``
+        tensor per segment, none of them its base's own storage. The accumulator is not touched; the
+        NaN flags are the caller's to read (``raise_on_nan``). With ``check_indices`` the call then
+        waits for the stream and raises ``ValueError`` if an index array is not strictly increasing
+        inside its tensor (the outputs are unspecified then, nothing outside them was written; a NaN
+        flag that the same fold latched stays latched, since clearing it is ``reset()``, which also
+        forgets the accumulator: a caller that keeps the context reads ``flags()`` and resets).
+        Refused before any launch: no clients, more than 1024, a delta that does not match its
+        segment, mixed value dtypes, a non-finite weight, a divisor that is not finite and > 0, a
+        base or an output that does not match, an output that is its base."""
+        T = self.layout.num_segments
+        ocode = out_code(out_dtype)
+        table = rows if isinstance(rows, SparseTable) else SparseTable(rows, self.layout, self.device)
+        if table.layout != self.layout or table.device != self.device:
+            raise ValueError("the sparse table was built for another layout or device")
+        n, iptr, vptr, nnz, vcode = table.num_clients, table.iptr, table.vptr, table.nnz, dtype_code(table.dtype)
+        w = np.ascontiguousarray([float(x) for x in weights], dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f"one weight per client is required: {w.size} for {n} clients")
+        if not np.isfinite(w).all():
+            raise ValueError("the weights must be finite")
+        divisor = float(divisor)
+        if not (divisor > 0 and math.isfinite(divisor)):
+            raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
+        if len(base) != T or len(outs) != T:
+            raise ValueError("one base tensor and one output tensor per segment are required")
+        for t, (z, o, numel) in enumerate(zip(base, outs, self.layout.numels)):
+            if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
+                raise ValueError(f"base tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
+            if o.dtype != out_dtype or o.device != self.device or o.numel() != numel or not o.is_contiguous():
+                raise ValueError(
+                    f"output tensor {t}: contiguous {out_dtype} of {numel} elements on {self.device} is required")
+            if o.data_ptr() == z.data_ptr():
+                raise ValueError(f"output tensor {t} is its base: the sparse fold is not in-place")
+        zp = (ctypes.c_void_p * T)(*[z.data_ptr() for z in base])
+        op = (ctypes.c_void_p * T)(*[o.data_ptr() for o in outs])
+        _native.check(
+            self._lib.fedavg_sparse_aggregate_delta(
+                self._h, iptr.ctypes.data_as(_PTR), vptr.ctypes.data_as(_PTR),
+                nnz.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), vcode, w.ctypes.data_as(_DBL), n, divisor, zp, op,
+                ocode, self.stream,
+            )
+        )
+        if check_indices and self.sparse_index_errors():
+            raise ValueError(SPARSE_INDEX_MESSAGE)
+
+    def sparse_index_errors(self) -> bool:
+        """Wait for the stream and report (once) whether a sparse fold since the last report met an
+        index violation (``fedavg_sparse_index_errors``)."""
+        out = ctypes.c_int32()
+        _native.check(self._lib.fedavg_sparse_index_errors(self._h, self.stream, ctypes.byref(out)))
+        return bool(out.value)
 
     def server_opt_step(self, table: ClientTable, in_dtype: torch.dtype, coefficients: Sequence[float],
                         divisor: float, point: Sequence[torch.Tensor], m_in: Sequence[torch.Tensor],

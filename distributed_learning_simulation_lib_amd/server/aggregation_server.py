@@ -35,6 +35,7 @@ from ..message import (
     wire_class,
 )
 from ..quantized import dequantize_parameter, is_quantized
+from ..sparse import densify_parameter, is_sparse
 
 
 class ModelCache:
@@ -148,6 +149,7 @@ class AggregationServer:
                     return
             old_parameter = self._model_cache.parameter
             self._dequantize_if_needed(data)
+            self._densify_if_needed(data)
             if is_delta_message(data):
                 assert old_parameter is not None
                 if getattr(self._algorithm, "accepts_delta_messages", False):
@@ -177,6 +179,15 @@ class AggregationServer:
         elif is_parameter_message(data) and is_quantized(data.parameter):
             if not getattr(self._algorithm, "accepts_quantized_messages", False):
                 data.parameter = dequantize_parameter(data.parameter)
+
+    def _densify_if_needed(self, data: Message) -> None:
+        """A delta that holds ``sparse.SparseDelta`` values (top-k clients) is handed over as it is to
+        an algorithm with ``accepts_sparse_messages`` (SparseFedAVGAlgorithm folds the entries
+        themselves); for every other algorithm the sparse values are densified — missing entries
+        are +0.0 — so the delta then takes the existing delta / restore branch unchanged."""
+        if is_delta_message(data) and is_sparse(data.delta_parameter):
+            if not getattr(self._algorithm, "accepts_sparse_messages", False):
+                data.delta_parameter = densify_parameter(data.delta_parameter)
 
     def _aggregate_worker_data(self) -> Message:
         self._algorithm.set_old_parameter(self._model_cache.parameter)

@@ -140,7 +140,10 @@ int32_t fedavg_build_flags(void);
  * "trust_max_clients" and "trust_ae_<d>" (elements of one 16-byte load) of
  * fedavg_moments_about_point;
  * "opt_tile" (elements per workgroup), "opt_threads", "opt_max_clients" and "opt_ae_<d>" (elements
- * of one 16-byte load) of fedavg_server_opt_step.
+ * of one 16-byte load) of fedavg_server_opt_step;
+ * "sparse_tile" (elements per workgroup), "sparse_threads", "sparse_batch" (clients between two
+ * pairs of workgroup barriers = LDS planes: it does not enter the result) and "sparse_max_clients"
+ * of fedavg_sparse_aggregate_delta.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -599,6 +602,65 @@ int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* client_ptrs, 
                                double beta2, double one_minus_beta2, double tau,
                                void* const* out_ptrs /* [num_segments], device */,
                                int32_t out_dtype, void* stream);
+
+/*
+ * The sparse delta fold: FedAvg over clients that send, per tensor, nnz (index, value) pairs of a
+ * parameter diff against the server's cached global model (top-k sparsification with error
+ * feedback on the client). A sparse delta is a DeltaParameterMessage whose missing entries are
+ * +0.0, so the result is the reference's restore() (message.py:40-61) followed by FedAVGAlgorithm
+ * (fed_avg_algorithm.py:43-99) on the densified delta, bit for bit, and bit for bit what
+ * fedavg_aggregate_delta gives on the densified tensors. The contract is DESIGN.md §5n, restated
+ * independently in tests/sparse_reference.py.
+ *
+ * index_ptrs[num_clients][num_segments] and value_ptrs[num_clients][num_segments] are host arrays of
+ * device pointers; nnz[num_clients][num_segments] is a host array, 0 <= nnz <= the segment's element
+ * count. An index array holds nnz STRICTLY INCREASING int32 flat positions in [0, element count),
+ * 4-byte aligned; a value array nnz values of value_dtype (FEDAVG_F32 / F16 / BF16 / F64), aligned to
+ * the element; both may be NULL only where nnz == 0. weights[num_clients] is a host array.
+ * base_ptrs[num_segments] are fp64 tensors of the segments' element counts, 8-byte aligned (the
+ * cached global model); out_ptrs[num_segments] out_dtype (FEDAVG_F32 / F64) tensors of the same
+ * counts. Per element e of every segment, with b the base and w the weights:
+ *   d_i = the value client i stores for e, converted exactly to fp64, or +0.0 if it has none
+ *   x_i = b[e] + d_i   (performed even for d_i = +0.0, so b = -0.0 gives +0.0)
+ *   p_i = x_i * w_i;  acc = p_0, then acc = acc + p_i for i = 1 .. n - 1 in table order
+ *   out[e] = acc / divisor   (IEEE division)
+ * every line one separately rounded fp64 operation: NO FMA, no leading 0 +. An fp32 output is the
+ * fp64 result rounded to nearest even. The result depends on the element's base value, the entries
+ * that name it, the weights in table order and the divisor alone: never on the tiling, the client
+ * batch ("sparse_batch"), other elements, the device, timing or earlier calls (no atomics).
+ * Asynchronous on `stream`; the accumulator and its state are not touched.
+ * A NaN in any x_i (a NaN value, a NaN base, inf - inf) latches FEDAVG_FLAG_INPUT_NAN; a NaN in acc
+ * latches FEDAVG_FLAG_ACC_NAN; a NaN in the fp64 result latches FEDAVG_FLAG_RESULT_NAN. fedavg_check
+ * reports the flags.
+ * Index violations (an index that is negative, >= the element count, or not greater than its
+ * predecessor) are an input error: a pass over the index arrays in the same call latches a word of
+ * the context's sparse state (not the NaN words), which fedavg_sparse_index_errors reports. The fold
+ * is safe whatever the indices are: an entry reaches a tile only after its index has been checked to
+ * lie inside that tile, otherwise it is dropped; nothing outside an output tensor is written and
+ * nothing outside [0, nnz) of an index or value array is read. The outputs of a call that reports a
+ * violation are unspecified.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a NULL table; a NULL index or value array with
+ * nnz > 0; a bad dtype; a pointer not aligned to its element; nnz outside [0, element count];
+ * num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS; a non-finite weight; a divisor that is not finite
+ * and > 0; out_ptrs[t] == base_ptrs[t]; a segment of more than 2^31 - 1 elements), FEDAVG_ERR_STATE
+ * (an open dynamic wave).
+ */
+int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx,
+                                      const int32_t* const* index_ptrs /* [n][num_segments], device */,
+                                      const void* const* value_ptrs /* [n][num_segments], device */,
+                                      const int64_t* nnz /* [n][num_segments], host */,
+                                      int32_t value_dtype, const double* weights /* [n], host */,
+                                      int32_t num_clients, double divisor,
+                                      const double* const* base_ptrs /* [num_segments], device fp64 */,
+                                      void* const* out_ptrs /* [num_segments], device */,
+                                      int32_t out_dtype, void* stream);
+
+/*
+ * Synchronise `stream` and report whether a sparse fold since the last report met an index
+ * violation: *out = 1 if so, else 0. The word is cleared by the report, so the context stays usable.
+ * FEDAVG_ERR_INVALID for a NULL context or out.
+ */
+int32_t fedavg_sparse_index_errors(fedavg_ctx* ctx, void* stream, int32_t* out);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
