@@ -3572,7 +3572,7 @@ int32_t fedavg_partial(fedavg_ctx* c, const void* const* client_ptrs, int32_t in
   Staged st;
   FEDAVG_RET(stage_tables(c, s, K > 0 ? client_ptrs : nullptr, weights, K, nullptr, nullptr,
                           c->valid.data(), st));
-  // tile ranges are defined on the 2048-element tiles: the exact-order kernel
+  // tile ranges are defined on the kTile1 (4096-element) tiles: the exact-order kernel
   return launch_main(c, s, st, K > 0 ? in_dtype : FEDAVG_F32, OUT_ACC, 1, zero_init ? 1 : 0, tb, te);
 }
 
