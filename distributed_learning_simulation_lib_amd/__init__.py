@@ -12,9 +12,13 @@ from .algorithm import (
     AggregationAlgorithm,
     BulyanFedAVGAlgorithm,
     ClippedFedAVGAlgorithm,
+    CompositeAggregationAlgorithm,
     FedAVGAlgorithm,
     FLTrustFedAVGAlgorithm,
     GeometricMedianFedAVGAlgorithm,
+    GraphAlgorithm,
+    GraphNodeEmbeddingPassingAlgorithm,
+    GraphTopologyAlgorithm,
     KrumFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
@@ -41,12 +45,16 @@ __all__ = [
     "BulyanFedAVGAlgorithm",
     "ClientTable",
     "ClippedFedAVGAlgorithm",
+    "CompositeAggregationAlgorithm",
     "DeltaParameterMessage",
     "FeatureMessage",
     "FedAVGAlgorithm",
     "FLTrustFedAVGAlgorithm",
     "FedAvgContext",
     "GeometricMedianFedAVGAlgorithm",
+    "GraphAlgorithm",
+    "GraphNodeEmbeddingPassingAlgorithm",
+    "GraphTopologyAlgorithm",
     "KrumFedAVGAlgorithm",
     "Message",
     "ModelLayout",
@@ -164,6 +172,16 @@ def _register_builtin() -> None:
             client_cls=None,  # type: ignore[arg-type]
             server_cls=AggregationServer,
             algorithm_cls=SparseFedAVGAlgorithm,
+        )
+    # the reference's federated-GNN server (graph_worker): topology exchange, embedding exchange, FedAvg
+    if not AlgorithmRepository.has_algorithm("fed_graph"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_graph",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=GraphAlgorithm,
         )
 
 

@@ -41,6 +41,9 @@ ROBUST_MAX_CLIENTS = 64
 KRUM_MAX_CLIENTS = 256  # FEDAVG_KRUM_MAX_CLIENTS: fedavg_pairwise_sqdist
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
 # fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta
+ROUTE_MAX_SOURCES = 1024  # fedavg_route_rows
+ROUTE_MAX_NODE_SPACE = 1 << 28
+ROUTE_ERR_DUPLICATE, ROUTE_ERR_ORDER, ROUTE_ERR_RANGE = 1, 2, 4  # bits of fedavg_route_errors
 OPT_AVGM, OPT_ADAGRAD, OPT_YOGI, OPT_ADAM = 0, 1, 2, 3  # FEDAVG_OPT_*: fedavg_server_opt_step modes
 ABI_VERSION = 1
 ACC_ALIGN = 32  # FEDAVG_ACC_ALIGN: accumulator segments start at multiples of 32 elements
@@ -160,6 +163,13 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_pers_prof_enable": (c_int32, [c_void_p, c_int32]),
     "fedavg_pers_prof_collect": (c_int32, [c_void_p, _PD, POINTER(c_int32)]),
     "fedavg_fp64_probe": (c_int32, [c_int64, c_int32, _PD, c_void_p]),
+    # the routed row gather (route_kernels.hip); tables and device arrays as raw addresses
+    "fedavg_route_create": (c_int32, [POINTER(c_void_p), c_int32]),
+    "fedavg_route_destroy": (c_int32, [c_void_p]),
+    "fedavg_route_rows": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fedavg_route_errors": (c_int32, [c_void_p, c_void_p, POINTER(c_int32)]),
     # host ingest (host_pack.cpp)
     "fedavg_host_pack": (c_int32, [c_void_p, _PP, POINTER(c_int64), POINTER(c_int64), c_int32]),
     "fedavg_host_pack_threads": (c_int32, []),

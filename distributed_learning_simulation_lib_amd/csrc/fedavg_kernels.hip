@@ -45,6 +45,7 @@
 #include "point_internal.h"
 #include "clip_internal.h"
 #include "sparse_internal.h"
+#include "route_internal.h"
 #include "trust_internal.h"
 #include "opt_internal.h"
 
@@ -3045,6 +3046,8 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
     if (fedavg_internal_opt_constant(name, &v) != FEDAVG_OK) v = -1;
   } else if (n.rfind("sparse_", 0) == 0) {
     if (fedavg_internal_sparse_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (n.rfind("route_", 0) == 0) {
+    if (fedavg_internal_route_constant(name, &v) != FEDAVG_OK) v = -1;
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);

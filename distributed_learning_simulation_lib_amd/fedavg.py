@@ -1531,3 +1531,59 @@ def bw_probe(src: torch.Tensor, dst: torch.Tensor, mode: int) -> None:
             _stream_handle(src.device),
         )
     )
+
+
+class RowRouter:
+    """One native routing handle (``fedavg_route_*`` of ``include/fedavg_hip.h``): the dense table
+    node -> sent row, the call's workspace and the error bits, on one device. It owns no model
+    layout. Calls launch on the current torch stream of the device; one stream at a time."""
+
+    def __init__(self, device: torch.device | str | int | None = None, lib: ctypes.CDLL | None = None) -> None:
+        self._lib = lib if lib is not None else _native.load()
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("the routed row gather runs on a GPU device")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        handle = ctypes.c_void_p()
+        _native.check(self._lib.fedavg_route_create(ctypes.byref(handle), device.index))
+        self._h = handle
+
+    def route_rows(self, sources: Sequence[torch.Tensor], src_ids: torch.Tensor | None, want_ids: torch.Tensor | None,
+                   want_off: np.ndarray, node_space: int, out_rows: torch.Tensor | None, out_ids: torch.Tensor | None,
+                   out_count: torch.Tensor, row_bytes: int, elem_bytes: int) -> None:
+        """One ``fedavg_route_rows`` call. ``sources`` are contiguous row blocks on the device
+        (``sources[s][i]`` is a row of ``row_bytes`` bytes), ``src_ids`` / ``want_ids`` / ``out_ids``
+        int64 device tensors, ``want_off`` a host int64 array of ``len(out_count) + 1`` offsets and
+        ``out_count`` an int32 device tensor. The library validates the rest."""
+        S = len(sources)
+        ptrs = np.fromiter((t.data_ptr() for t in sources), dtype=np.uint64, count=S)
+        rows = np.fromiter((t.shape[0] for t in sources), dtype=np.int64, count=S)
+        want_off = np.ascontiguousarray(want_off, dtype=np.int64)
+
+        def addr(t: torch.Tensor | None) -> int | None:
+            return None if t is None else t.data_ptr()
+
+        _native.check(self._lib.fedavg_route_rows(
+            self._h, ptrs.ctypes.data if S else None, rows.ctypes.data if S else None, S, row_bytes, elem_bytes,
+            addr(src_ids), addr(want_ids), want_off.ctypes.data, len(want_off) - 1, node_space, addr(out_rows),
+            addr(out_ids), addr(out_count), _stream_handle(self.device)))
+
+    def errors(self) -> int:
+        """Wait for the stream, report the error bits latched since the last report
+        (``_native.ROUTE_ERR_*``) and clear them."""
+        out = ctypes.c_int32(0)
+        _native.check(self._lib.fedavg_route_errors(self._h, _stream_handle(self.device), ctypes.byref(out)))
+        return int(out.value)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.fedavg_route_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self) -> None:  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass

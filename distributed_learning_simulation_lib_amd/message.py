@@ -135,6 +135,11 @@ def is_delta_message(obj: Any) -> bool:
     return "delta_parameter" in _field_names(obj) and is_parameter_message_base(obj)
 
 
+def is_feature_message(obj: Any) -> bool:
+    """FeatureMessage (message.py:64-66): a Message with a ``feature`` tensor (or None)."""
+    return "feature" in _field_names(obj) and is_message(obj)
+
+
 KIND_OTHER, KIND_PARAMETER, KIND_DELTA = 0, 1, 2
 _KIND_CACHE: dict[type, int] = {}
 

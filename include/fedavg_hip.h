@@ -143,7 +143,9 @@ int32_t fedavg_build_flags(void);
  * of one 16-byte load) of fedavg_server_opt_step;
  * "sparse_tile" (elements per workgroup), "sparse_threads", "sparse_batch" (clients between two
  * pairs of workgroup barriers = LDS planes: it does not enter the result) and "sparse_max_clients"
- * of fedavg_sparse_aggregate_delta.
+ * of fedavg_sparse_aggregate_delta;
+ * "route_chunk" (wanted ids per workgroup of the rank walk), "route_threads", "route_max_sources" and
+ * "route_max_node_space" of fedavg_route_rows.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -725,6 +727,68 @@ int32_t fedavg_pers_prof_enable(fedavg_pers* p, int32_t enable);
 int32_t fedavg_pers_prof_collect(fedavg_pers* p, double* total_ms, int32_t* launches);
 /* fp64 VALU ceiling probe (independent v_fma_f64 chains): measured TFLOP/s */
 int32_t fedavg_fp64_probe(int64_t waves, int32_t iters, double* tflops_out, void* stream);
+
+/* =====================================================================================
+ * The routed row gather: the server half of the reference's graph embedding exchange
+ * (GraphNodeEmbeddingPassingAlgorithm, simulation_lib/algorithm/graph_embedding_algorithm.py:38-59).
+ * S workers send row blocks whose rows carry node ids; N workers each want a list of node ids and
+ * get back, packed, the ids that somebody sent and those nodes' rows. A routed copy and nothing
+ * else: no arithmetic touches a row, so every output byte is a source byte. The contract is
+ * DESIGN.md §5o, restated independently in tests/graph_reference.py.
+ *
+ * A routing does not depend on a model layout, so it has a handle of its own. The handle owns the
+ * dense int32 table node -> sent row (grown on demand, empty between calls), the call's workspace
+ * and the error words; it serves one stream at a time (calls on several streams need the caller's
+ * ordering).
+ *
+ * src_ptrs[num_sources] is a host array of device pointers to contiguous row blocks of
+ * src_rows[num_sources] rows (host; 0 allowed, the pointer may then be NULL) of one common row_bytes;
+ * elem_bytes (1, 2, 4 or 8) divides row_bytes and every row block is aligned to it. src_ids is a
+ * device int64 array of R = sum(src_rows) node ids in source order: row r of the concatenation
+ * carries node src_ids[r]; every id lies in [0, node_space) and no id appears twice. want_ids is a
+ * device int64 array of B ids, the N = num_lists want lists concatenated; want_off[N + 1] (host)
+ * cuts it, and every list is STRICTLY INCREASING. For list j let H_j be its ids that some source
+ * sent, in the list's own order. Then
+ *   out_count[j] = |H_j|                                  (device int32 [N])
+ *   out_ids[want_off[j] + k] = the k-th id of H_j          (device int64 [B])
+ *   out_rows row want_off[j] + k = that node's source row, unchanged   (device, B * row_bytes)
+ * Every list packs into its own slot, which begins at want_off[j]: no count has to be known before
+ * the outputs are allocated. Slots past the count are unspecified (this implementation leaves them
+ * untouched) and nothing outside the three buffers is ever written. A wanted id that is negative,
+ * >= node_space or sent by nobody is a miss; the table is never read out of range for it. With
+ * num_sources = 0 every list misses everything. The result depends on the inputs alone: never on
+ * the chunking ("route_chunk"), timing or earlier calls (no atomics; the table is put back to empty
+ * by un-scattering the sent ids before the call's work on the stream ends, error or not).
+ * Rows move by 16-byte loads and stores when row_bytes, out_rows and every source block are
+ * multiples of 16, else element by element, with the same bytes out.
+ * Asynchronous on `stream`.
+ * Input errors found on the device latch bits that fedavg_route_errors reports: 1 = a node id was
+ * sent twice (found by write-then-verify), 2 = a want list is not strictly increasing, 4 = a sent
+ * id lies outside [0, node_space) (the row is then nobody's). The outputs of such a call are
+ * unspecified but stay inside the buffers, and the handle stays usable.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a NULL handle or table; num_sources < 0 or > 1024;
+ * num_lists < 1; a bad elem_bytes; row_bytes < 1 or not a multiple of elem_bytes; a pointer not
+ * aligned to its element; a negative src_rows entry; R or B >= 2^31; node_space < 0 or > 2^28 (a
+ * 1 GiB table); want_off not non-decreasing from 0).
+ * ===================================================================================== */
+typedef struct fedavg_route fedavg_route;
+int32_t fedavg_route_create(fedavg_route** out, int32_t device);
+int32_t fedavg_route_destroy(fedavg_route* route);
+int32_t fedavg_route_rows(fedavg_route* route,
+                          const void* const* src_ptrs /* [num_sources], host array of device pointers */,
+                          const int64_t* src_rows /* [num_sources], host */, int32_t num_sources,
+                          int64_t row_bytes, int32_t elem_bytes,
+                          const int64_t* src_ids /* [R], device */,
+                          const int64_t* want_ids /* [B], device */,
+                          const int64_t* want_off /* [num_lists + 1], host */, int32_t num_lists,
+                          int64_t node_space, void* out_rows /* device, B * row_bytes */,
+                          int64_t* out_ids /* [B], device */, int32_t* out_count /* [num_lists], device */,
+                          void* stream);
+/*
+ * Synchronise `stream`, report the error bits latched since the last report (see fedavg_route_rows)
+ * into *out and clear them. FEDAVG_ERR_INVALID for a NULL handle or out.
+ */
+int32_t fedavg_route_errors(fedavg_route* route, void* stream, int32_t* out);
 
 /* =====================================================================================
  * Host ingest (aggregation_server.py:129: updates arrive as CPU tensors). Copy one client's
