@@ -37,11 +37,13 @@ from .message import (
     ParameterMessageBase,
     get_message_size,
 )
+from .quantized import BroadcastQuantizer, philox_uniforms
 from .sparse import SparseDelta, topk_sparsify
 
 __all__ = [
     "AggregationAlgorithm",
     "AlgorithmRepository",
+    "BroadcastQuantizer",
     "BulyanFedAVGAlgorithm",
     "ClientTable",
     "ClippedFedAVGAlgorithm",
@@ -69,6 +71,7 @@ __all__ = [
     "SparseDelta",
     "SparseFedAVGAlgorithm",
     "get_message_size",
+    "philox_uniforms",
     "topk_sparsify",
 ]
 

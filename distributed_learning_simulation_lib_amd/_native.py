@@ -142,6 +142,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_sparse_aggregate_delta": (
         c_int32, [c_void_p, _PP, _PP, POINTER(c_int64), c_int32, _PD, c_int32, c_double, _PP, _PP, c_int32, c_void_p]),
     "fedavg_sparse_index_errors": (c_int32, [c_void_p, c_void_p, POINTER(c_int32)]),
+    # the broadcast encoder (quant_kernels.hip); tables as raw addresses
+    "fedavg_quant_encode": (
+        c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_double,
+                  ctypes.c_uint64, c_uint32, c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

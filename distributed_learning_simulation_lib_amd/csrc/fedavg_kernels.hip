@@ -46,6 +46,7 @@
 #include "clip_internal.h"
 #include "sparse_internal.h"
 #include "route_internal.h"
+#include "quant_internal.h"
 #include "trust_internal.h"
 #include "opt_internal.h"
 
@@ -2262,6 +2263,8 @@ struct fedavg_ctx {
   // per-context state of the sparse delta fold (sparse_kernels.hip: tile table, table staging,
   // the index-violation word)
   void* sparse = nullptr;
+  // per-context state of the broadcast encoder (quant_kernels.hip: table staging, tile partials)
+  void* quant = nullptr;
   // the dynamic wave (fedavg_dyn_*): its host-coherent control block and row table, the device
   // mirror words, a private stream (the caller's stream stays free for the work producing the
   // arrivals) and the per-segment totals of the published rows
@@ -3048,6 +3051,8 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
     if (fedavg_internal_sparse_constant(name, &v) != FEDAVG_OK) v = -1;
   } else if (n.rfind("route_", 0) == 0) {
     if (fedavg_internal_route_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (n.rfind("quant_", 0) == 0) {
+    if (fedavg_internal_quant_constant(name, &v) != FEDAVG_OK) v = -1;
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);
@@ -3283,6 +3288,7 @@ int32_t fedavg_ctx_destroy(fedavg_ctx* c) {
   if (c->trust) fedavg_internal_trust_release(c->device, c->trust);
   if (c->opt) fedavg_internal_opt_release(c->device, c->opt);
   if (c->sparse) fedavg_internal_sparse_release(c->device, c->sparse);
+  if (c->quant) fedavg_internal_quant_release(c->device, c->quant);
   delete c;
   return FEDAVG_OK;
 }
@@ -3532,6 +3538,12 @@ int32_t fedavg_internal_opt_slot(fedavg_ctx* c, void*** slot) {
 int32_t fedavg_internal_sparse_slot(fedavg_ctx* c, void*** slot) {
   FEDAVG_RET(check_ctx(c));
   *slot = &c->sparse;
+  return FEDAVG_OK;
+}
+
+int32_t fedavg_internal_quant_slot(fedavg_ctx* c, void*** slot) {
+  FEDAVG_RET(check_ctx(c));
+  *slot = &c->quant;
   return FEDAVG_OK;
 }
 

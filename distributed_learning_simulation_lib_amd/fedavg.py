@@ -1159,6 +1159,50 @@ class FedAvgContext:
         if check_indices and self.sparse_index_errors():
             raise ValueError(SPARSE_INDEX_MESSAGE)
 
+    def quant_encode(self, codec: int, tensors: Sequence[torch.Tensor], records: Sequence[torch.Tensor],
+                     level: int = 255, weight: float = 0.01, seed: int = 0, draw: int = 0,
+                     tensor_ids: Sequence[int] | None = None) -> None:
+        """Encode ``tensors`` (contiguous fp32 or fp64 tensors of one dtype on the context's device,
+        of any sizes: the context's layout plays no part) into QSGD or NNADQ records in three
+        launches (``fedavg_quant_encode``). ``codec`` is one of ``_native.QSGD_F32 /
+        QSGD_F64 / NNADQ_F32 / NNADQ_F64`` and names the tensors' dtype; ``records[t]`` is a 16-byte
+        aligned uint8 tensor of the record's size, every byte of which is written (it may be
+        uninitialised). ``tensor_ids[t]`` is the tensor's word of the uniform stream's counter
+        (default: its position). Asynchronous; a non-finite element latches the input flag, which
+        ``raise_on_nan`` turns into ``NaNAggregationError``."""
+        if codec not in _native.RECORD_CODES:
+            raise ValueError(f"codec {codec} is not a record format")
+        f64 = codec in (_native.QSGD_F64, _native.NNADQ_F64)
+        nnadq = codec in (_native.NNADQ_F32, _native.NNADQ_F64)
+        dt = torch.float64 if f64 else torch.float32
+        T = len(tensors)
+        if T == 0 or len(records) != T:
+            raise ValueError("one record per tensor and at least one tensor are required")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
+            raise ValueError("the seed is a uint64 and the draw a uint32")
+        ids = np.arange(T, dtype=np.uint32) if tensor_ids is None else np.ascontiguousarray(tensor_ids, dtype=np.uint32)
+        if ids.shape != (T,):
+            raise ValueError("one stream id per tensor is required")
+        iptr = np.zeros(T, dtype=np.uint64)
+        rptr = np.zeros(T, dtype=np.uint64)
+        numels = np.zeros(T, dtype=np.int64)
+        for t, (x, r) in enumerate(zip(tensors, records)):
+            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"tensor {t}: a contiguous {dt} tensor on {self.device} is required")
+            n = x.numel()
+            need = 32 + (n + 15) // 16 * 16 if nnadq else 16 + (n + 15) // 16 * 16 + ((n + 7) // 8 + 15) // 16 * 16
+            if r.dtype != torch.uint8 or r.device != self.device or not r.is_contiguous() or r.numel() != need:
+                raise ValueError(f"record {t}: a contiguous uint8 tensor of {need} bytes on {self.device} is required")
+            iptr[t] = x.data_ptr() if n else 0
+            rptr[t] = r.data_ptr()
+            numels[t] = n
+        _native.check(
+            self._lib.fedavg_quant_encode(
+                self._h, codec, iptr.ctypes.data, numels.ctypes.data, ids.ctypes.data, T, rptr.ctypes.data,
+                int(level), float(weight), int(seed), int(draw), self.stream,
+            )
+        )
+
     def sparse_index_errors(self) -> bool:
         """Wait for the stream and report (once) whether a sparse fold since the last report met an
         index violation (``fedavg_sparse_index_errors``)."""

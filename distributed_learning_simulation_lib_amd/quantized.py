@@ -35,10 +35,11 @@ import math
 from collections.abc import Callable, Mapping
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _native
-from .fedavg import ModelLayout
+from .fedavg import FedAvgContext, ModelLayout, NaNAggregationError
 
 _log = logging.getLogger(__name__)
 
@@ -356,3 +357,244 @@ class NeuralNetworkAdaptiveDeterministicDequant:
 def NNADQ(weight: float) -> tuple[NeuralNetworkAdaptiveDeterministicQuant, NeuralNetworkAdaptiveDeterministicDequant]:  # noqa: N802
     """The (quant, dequant) pair the NNADQ endpoints take (quantized_endpoint.py:117,135)."""
     return NeuralNetworkAdaptiveDeterministicQuant(weight), NeuralNetworkAdaptiveDeterministicDequant()
+
+
+# -- the broadcast encoder (QuantServerEndpoint.send, quantized_endpoint.py:79-96) ----------------
+#
+# The server quantises the aggregated model before it goes out to every worker. On a GPU the
+# records are written by fedavg_quant_encode (csrc/quant_kernels.hip, DESIGN.md §5p) where the
+# result lies; on the CPU the functions below produce the same bytes. QSGD's uniforms are a
+# defined stream, not torch.rand, so both paths and a test restatement agree bit for bit.
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def philox4x32(counter: np.ndarray, key: tuple[int, int]) -> np.ndarray:
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11) of ``counter`` (uint32 [..., 4]) under
+    ``key`` (two uint32 words): uint32 [..., 4]."""
+    c = [np.asarray(counter)[..., i].astype(np.uint64) for i in range(4)]
+    k0, k1 = int(key[0]) & _U32, int(key[1]) & _U32
+    m0, m1 = np.uint64(_PHILOX_M0), np.uint64(_PHILOX_M1)
+    mask, s32 = np.uint64(_U32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]  # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> s32) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> s32) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def _philox_uniforms_np(seed: int, draw: int, t: int, n: int, f64: bool) -> np.ndarray:
+    seed, draw, t = int(seed), int(draw), int(t)
+    if not 0 <= seed < 1 << 64 or not 0 <= draw < 1 << 32 or not 0 <= t < 1 << 32:
+        raise ValueError("the seed is a uint64, the draw and the tensor index are uint32")
+    per = 2 if f64 else 4
+    blocks = np.arange((n + per - 1) // per, dtype=np.uint64)
+    ctr = np.empty((blocks.size, 4), dtype=np.uint32)
+    ctr[:, 0] = (blocks & np.uint64(_U32)).astype(np.uint32)
+    ctr[:, 1] = (blocks >> np.uint64(32)).astype(np.uint32)
+    ctr[:, 2] = t
+    ctr[:, 3] = draw
+    out = philox4x32(ctr, (seed & _U32, seed >> 32))
+    if not f64:
+        return ((out >> np.uint32(8)).astype(np.float32) * np.float32(2.0**-24)).reshape(-1)[:n]
+    lo, hi = out[:, 0::2].astype(np.uint64), out[:, 1::2].astype(np.uint64)
+    m = ((hi >> np.uint64(5)) << np.uint64(26)) | (lo >> np.uint64(6))  # 53 bits: exact in fp64
+    return (m.astype(np.float64) * 2.0**-53).reshape(-1)[:n]
+
+
+def philox_uniforms(seed: int, draw: int, t: int, n: int, dtype: torch.dtype) -> torch.Tensor:
+    """The ``n`` uniforms in [0, 1) that the broadcast encoder's QSGD draws for tensor ``t``:
+    Philox4x32-10 with key ``(seed & 0xffffffff, seed >> 32)`` and counter ``(block & 0xffffffff,
+    block >> 32, t, draw)``. fp32: ``block = i // 4``, ``u = (out[i % 4] >> 8) * 2**-24``; fp64:
+    ``block = i // 2``, ``u = ((out[2 (i % 2) + 1] >> 5) * 2**26 + (out[2 (i % 2)] >> 6)) * 2**-53``.
+    A CPU tensor of ``dtype`` (fp32 or fp64)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"the uniform stream is defined for fp32 and fp64, not {dtype}")
+    return torch.from_numpy(_philox_uniforms_np(seed, draw, t, int(n), dtype == torch.float64).copy())
+
+
+def _total_order_extrema(v: np.ndarray) -> tuple[np.floating, np.floating]:
+    """(min, max) of a non-empty finite numpy vector with -0.0 < +0.0 (numpy's own min / max leave
+    the sign of a zero extremum to the order of the elements)."""
+    lo, hi = v.min(), v.max()
+    if lo == 0:
+        lo = v.dtype.type(-0.0 if np.any(np.signbit(v) & (v == 0)) else 0.0)
+    if hi == 0:
+        hi = v.dtype.type(0.0 if np.any(~np.signbit(v) & (v == 0)) else -0.0)
+    return lo, hi
+
+
+def _encode_host(v: np.ndarray, scheme: str, level: int, weight: float, seed: int, draw: int, t: int) -> np.ndarray:
+    """One record (numpy uint8) of the flat fp32 / fp64 numpy vector ``v``: the same operations,
+    each rounded in ``v``'s dtype, as quant_kernels.hip."""
+    dt = v.dtype.type
+    n = v.size
+    if not np.isfinite(v).all():
+        raise NaNAggregationError("input", f"tensor {t} of the model to broadcast holds a non-finite element")
+    if scheme == "nnadq":
+        rec = np.zeros(NNADQ_HEADER_BYTES + _align16(n), dtype=np.uint8)
+        lo, step, levels = dt(0), dt(0), 1
+        if n:
+            lo, hi = _total_order_extrema(v)
+            with np.errstate(all="ignore"):
+                dlo, dhi = np.float64(lo), np.float64(hi)
+                amax = max(abs(dlo), abs(dhi))
+                r = (dhi - dlo) / (np.float64(weight) * amax) if amax > 0 and weight > 0 else np.float64("nan")
+                if np.isfinite(r) and r > 0:
+                    levels = int(min(NNADQ_MAX_LEVELS, max(1, math.ceil(r))))
+                step = dt(hi - lo) / dt(levels)
+                if step > 0 and np.isfinite(step):
+                    codes = np.clip(np.rint((v - lo) / step), 0, levels).astype(np.uint8)
+                    rec[NNADQ_HEADER_BYTES : NNADQ_HEADER_BYTES + n] = codes
+        rec[0:8] = np.frombuffer(np.float64(lo).tobytes(), dtype=np.uint8)
+        rec[8:16] = np.frombuffer(np.float64(step).tobytes(), dtype=np.uint8)
+        rec[16:20] = np.frombuffer(np.int32(levels).tobytes(), dtype=np.uint8)
+        return rec
+    rec = np.zeros(record_bytes(n), dtype=np.uint8)
+    norm = dt(0)
+    if n:
+        lo, hi = _total_order_extrema(v)
+        norm = max(-lo, hi)
+        if norm > 0:
+            with np.errstate(all="ignore"):
+                r = (np.abs(v) / norm) * dt(level)
+                fl = np.floor(r)
+                u = _philox_uniforms_np(seed, draw, t, n, v.dtype == np.float64)
+                slots = fl + (u < (r - fl))
+            rec[HEADER_BYTES : HEADER_BYTES + n] = np.clip(slots, 0, level).astype(np.uint8)
+        else:
+            norm = dt(0)
+        packed = np.packbits(~(v < 0))
+        so = sign_offset(n)
+        rec[so : so + packed.size] = packed
+    rec[0:8] = np.frombuffer(np.float64(norm).tobytes(), dtype=np.uint8)
+    rec[8:12] = np.frombuffer(np.int32(level).tobytes(), dtype=np.uint8)
+    return rec
+
+
+class BroadcastQuantizer:
+    """The server's broadcast encoder: ``quantizer(parameter, draw)`` turns a model into QSGD or
+    NNADQ records (``scheme``), what the reference's quantised server endpoints do in ``send`` once
+    ``use_quant()`` was called (quantized_endpoint.py:79-96).
+
+    Tensors on a GPU are encoded there by ``fedavg_quant_encode`` (three launches per dtype group
+    whatever the number of tensors) into one device blob that the quantizer keeps and reuses: the
+    records returned are views of it and stay valid until the next call on that device.
+    ``encode_to_host`` moves the blob to the host in one copy and returns records that own their
+    memory. Tensors on the CPU are encoded by a numpy path that gives the same bytes. The dict may
+    mix fp32 and fp64 tensors (encoded per dtype group); any other dtype is a ``TypeError``.
+
+    QSGD's uniforms are the stream of ``philox_uniforms(seed, draw, t, ...)`` with ``t`` the
+    tensor's position in the dict; ``draw`` is the caller's (the server passes its broadcast count,
+    so rounds do not repeat a stream). NNADQ is deterministic: ``seed`` and ``draw`` play no part. A
+    non-finite element is refused with ``NaNAggregationError`` (an ``AssertionError``), and no
+    record is handed out. ``use_l2_norm`` is not offered: its summation order is unpinned."""
+
+    def __init__(self, scheme: str = "qsgd", quantization_level: int = DEFAULT_LEVEL, weight: float = 0.01,
+                 seed: int = 0, use_l2_norm: bool = False) -> None:
+        if scheme not in ("qsgd", "nnadq"):
+            raise ValueError(f"unknown scheme {scheme!r}: 'qsgd' or 'nnadq'")
+        if use_l2_norm:
+            raise NotImplementedError("the broadcast encoder offers the max norm only: the l2 norm's "
+                                      "summation order is unpinned")
+        if not isinstance(quantization_level, int) or not 1 <= quantization_level <= 255:
+            raise ValueError("quantization_level must be an integer in [1, 255] (one byte per slot)")
+        weight = float(weight)
+        if not (weight > 0 and math.isfinite(weight)):
+            raise ValueError("weight must be a finite number > 0")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed must be a uint64")
+        self.scheme = scheme
+        self.quantization_level = quantization_level
+        self.weight = weight
+        self.seed = int(seed)
+        self._contexts: dict[torch.device, FedAvgContext] = {}
+        self._blobs: dict[torch.device, torch.Tensor] = {}
+
+    def _context(self, device: torch.device) -> FedAvgContext:
+        ctx = self._contexts.get(device)
+        if ctx is None:
+            # the encoder does not depend on a context's layout: a one-element layout carries the
+            # device, the stream order, the flag words and the call's workspace
+            ctx = self._contexts[device] = FedAvgContext(ModelLayout.flat(1, "quant"), device)
+        return ctx
+
+    def device_blob(self, device: torch.device | str) -> torch.Tensor | None:
+        """The uint8 blob that holds the records of the last call on ``device`` (None before the
+        first): every record of a call is written whole, so its content between calls is free."""
+        return self._blobs.get(torch.device(device))
+
+    def _blob(self, device: torch.device, nbytes: int) -> torch.Tensor:
+        blob = self._blobs.get(device)
+        if blob is None or blob.numel() < nbytes:
+            blob = self._blobs[device] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        return blob
+
+    def _plan(self, parameter: Mapping[str, torch.Tensor]) -> list[tuple[str, torch.Tensor, QuantizedDtype, int]]:
+        plan = []
+        for t, (name, value) in enumerate(parameter.items()):
+            if not isinstance(value, torch.Tensor) or value.dtype not in (torch.float32, torch.float64):
+                kind = value.dtype if isinstance(value, torch.Tensor) else type(value).__name__
+                raise TypeError(f"{name}: the broadcast encoder takes fp32 and fp64 tensors, not {kind}")
+            plan.append((name, value.detach(), codec_for(value.dtype, self.scheme), t))
+        return plan
+
+    def __call__(self, parameter: Mapping[str, torch.Tensor], draw: int = 0) -> dict[str, QuantizedTensor]:
+        draw = int(draw)
+        if not 0 <= draw < 1 << 32:
+            raise ValueError("draw must be a uint32")
+        plan = self._plan(parameter)
+        out: dict[str, QuantizedTensor] = {}
+        by_device: dict[torch.device, list[tuple[str, torch.Tensor, QuantizedDtype, int]]] = {}
+        for item in plan:
+            by_device.setdefault(item[1].device, []).append(item)
+        for device, items in by_device.items():
+            if device.type == "cpu":
+                for name, value, codec, t in items:
+                    v = value.contiguous().reshape(-1).numpy()
+                    rec = _encode_host(v, self.scheme, self.quantization_level, self.weight, self.seed, draw, t)
+                    out[name] = QuantizedTensor(torch.from_numpy(rec), tuple(value.shape), codec)
+            else:
+                out.update(self._encode_device(device, items, draw))
+        return {name: out[name] for name in parameter}  # the model's own key order
+
+    def _encode_device(self, device: torch.device, items: list[tuple[str, torch.Tensor, QuantizedDtype, int]],
+                       draw: int) -> dict[str, QuantizedTensor]:
+        ctx = self._context(device)
+        sizes = [codec.record_bytes(value.numel()) for _, value, codec, _ in items]  # multiples of 16
+        blob = self._blob(device, sum(sizes))
+        views, off = [], 0
+        for size in sizes:
+            views.append(blob[off : off + size])
+            off += size
+        flat = [value.contiguous().reshape(-1) for _, value, _, _ in items]
+        for code in sorted({codec.code for _, _, codec, _ in items}):
+            group = [i for i, item in enumerate(items) if item[2].code == code]
+            ctx.quant_encode(code, [flat[i] for i in group], [views[i] for i in group], self.quantization_level,
+                             self.weight, self.seed, draw, [items[i][3] for i in group])
+        ctx.raise_on_nan()  # waits for the stream; a non-finite element is an AssertionError
+        return {name: QuantizedTensor(views[i], tuple(value.shape), codec)
+                for i, (name, value, codec, _) in enumerate(items)}
+
+    def encode_to_host(self, parameter: Mapping[str, torch.Tensor], draw: int = 0) -> dict[str, QuantizedTensor]:
+        """``self(parameter, draw)`` with every record on the host: a device's records cross in one
+        copy of its blob, and the host records do not alias the quantizer's reused device blob."""
+        records = self(parameter, draw)
+        out: dict[str, QuantizedTensor] = {}
+        host_blobs: dict[torch.device, torch.Tensor] = {}
+        for name, q in records.items():
+            if q.record.device.type == "cpu":
+                out[name] = q
+                continue
+            blob = self._blobs[q.record.device]
+            host = host_blobs.get(q.record.device)
+            if host is None:
+                used = max(r.record.storage_offset() + r.record.numel() for r in records.values()
+                           if r.record.device == q.record.device)
+                host = host_blobs[q.record.device] = blob[:used].to("cpu")
+            off = q.record.storage_offset()
+            # a record of its own storage: a transport that pickles tensors sends a view's whole storage
+            out[name] = QuantizedTensor(host[off : off + q.record.numel()].clone(), q.shape, q.codec)
+        return out

@@ -106,8 +106,14 @@ class AggregationServer:
         round_number: int = 1,
         init_parameter: dict[str, torch.Tensor] | None = None,
         config: Any = None,
+        broadcast_quantizer: Callable[..., dict[str, Any]] | None = None,
     ) -> None:
         self.worker_number = worker_number
+        # quantized.BroadcastQuantizer (or any ``(parameter, draw) -> records``): what the reference's
+        # quantised server endpoints do in ``send`` once ``use_quant()`` was called
+        # (topology/quantized_endpoint.py:79-96). None: the dense fp64 host copy goes out.
+        self._broadcast_quantizer = broadcast_quantizer
+        self._broadcast_count = 0  # the ``draw`` of the next quantised broadcast (the initial model: 0)
         self._endpoint = endpoint
         self.round_number = round_number
         self._round_index = 1
@@ -194,7 +200,12 @@ class AggregationServer:
         return self._algorithm.aggregate_worker_data()
 
     def _send_result(self, result: Message) -> None:
+        wire = None
         if is_parameter_message(result):
+            if self._broadcast_quantizer is not None:
+                # encoded from the algorithm's own (device) tensors, before anything moves to the host
+                # and before the cache changes: a refused model leaves the cached one in place
+                wire = self._quantize_broadcast(result)
             self._model_cache.cache_parameter(result.parameter)
             # what crosses the process boundary is the cached host copy
             result = wire_class(result, "ParameterMessage")(
@@ -210,10 +221,26 @@ class AggregationServer:
             self.round_seconds.append(time.perf_counter() - self._round_t0)
             self._round_t0 = None
         if self._endpoint is not None:
-            self._endpoint.broadcast(result)
+            self._endpoint.broadcast(wire if wire is not None else result)
         if not result.in_round:
             self._round_index += 1
         self._algorithm.clear_worker_data()
+
+    def _quantize_broadcast(self, result: Message) -> Message:
+        """The message that goes out in place of the dense one: host records of ``result.parameter``
+        and ``other_data["quantized"] = True``, as QuantServerEndpoint.send marks it
+        (quantized_endpoint.py:87-88). ``self.results`` and the ModelCache keep the full precision."""
+        quantizer = self._broadcast_quantizer
+        encode = getattr(quantizer, "encode_to_host", quantizer)
+        records = encode(result.parameter, self._broadcast_count)
+        self._broadcast_count += 1
+        return wire_class(result, "ParameterMessage")(
+            parameter=records,
+            end_training=result.end_training,
+            in_round=result.in_round,
+            other_data={**result.other_data, "quantized": True},
+            is_initial=result.is_initial,
+        )
 
     # -- server.py:122-152 (poll loop) -------------------------------------------------
     def start(self) -> None:

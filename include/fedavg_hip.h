@@ -145,7 +145,9 @@ int32_t fedavg_build_flags(void);
  * pairs of workgroup barriers = LDS planes: it does not enter the result) and "sparse_max_clients"
  * of fedavg_sparse_aggregate_delta;
  * "route_chunk" (wanted ids per workgroup of the rank walk), "route_threads", "route_max_sources" and
- * "route_max_node_space" of fedavg_route_rows.
+ * "route_max_node_space" of fedavg_route_rows;
+ * "quant_tile" (elements per workgroup), "quant_threads" and "quant_per_lane" (consecutive elements a
+ * lane encodes) of fedavg_quant_encode.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -663,6 +665,59 @@ int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx,
  * FEDAVG_ERR_INVALID for a NULL context or out.
  */
 int32_t fedavg_sparse_index_errors(fedavg_ctx* ctx, void* stream, int32_t* out);
+
+/*
+ * The broadcast encoder: the `send` half of the reference's StochasticQuantServerEndpoint /
+ * NNADQServerEndpoint (simulation_lib/topology/quantized_endpoint.py:79-96), which quantises the
+ * aggregated model before it goes out to every worker. num_tensors device tensors of one dtype are
+ * turned into QSGD or NNADQ records (the layouts of FEDAVG_QSGD_F32 / FEDAVG_NNADQ_F32 above) where
+ * they lie. The contract is DESIGN.md §5p, restated independently in tests/quant_encode_reference.py
+ * on top of oracle/qsgd_oracle.py and oracle/nnadq_oracle.py.
+ *
+ * codec: FEDAVG_QSGD_F32 / QSGD_F64 / NNADQ_F32 / NNADQ_F64; the codec's dtype F (fp32 or fp64) is
+ * the inputs' dtype. in_ptrs[num_tensors] (host array of device pointers): tensor t holds numels[t]
+ * (host, >= 0) elements of F, aligned to the element only (NULL allowed where numels[t] == 0).
+ * record_ptrs[num_tensors]: 16-byte aligned device buffers of fedavg_qsgd_record_bytes(numels[t]) /
+ * fedavg_nnadq_record_bytes(numels[t]) bytes. EVERY byte of every record is written (header gaps,
+ * the padding of the slot / code area and of the sign area as zeros): the buffers may be
+ * uninitialised. A tensor does not depend on the layout of the context, only on its own device.
+ *
+ * Every line below is one separately rounded operation in F: no FMA, no reciprocal, IEEE division.
+ *   QSGD:  norm = max|x|;  q = |x| / norm;  r = q * level;  fl = floor(r);  d = r - fl;
+ *          slot = fl + (u < d ? 1 : 0), 0 everywhere when norm == 0, clamped to [0, level];
+ *          sign bit = !(x < 0) (so -0.0 gives 1); header: norm widened to fp64, level.
+ *   NNADQ: lo = min x;  hi = max x;  in fp64: r = (hi - lo) / (weight * max(|lo|, |hi|)),
+ *          L = clamp(ceil(r), 1, 255), or 1 when r is not finite and positive;
+ *          step = (hi - lo) / L in F;  code = clamp(rint((x - lo) / step), 0, L) (half to even),
+ *          0 everywhere when step is not positive and finite; header: lo and step widened, L.
+ * lo and hi are the extrema in the IEEE total order (-0.0 < +0.0), max|x| = max(-lo, hi) with a
+ * zero norm stored as +0.0. An empty tensor gets norm 0 / lo 0, step 0, L 1.
+ *
+ * u is the uniform of element i of tensor t from Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57;
+ * Weyl constants 0x9E3779B9, 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and counter
+ * (block & 0xffffffff, block >> 32, id, draw), id = tensor_ids[t] (tensor_ids == NULL: id = t).
+ *   fp32: block = i / 4, u = (out[i % 4] >> 8) * 2^-24
+ *   fp64: block = i / 2, lo = out[2 * (i % 2)], hi = out[2 * (i % 2) + 1],
+ *         u = ((hi >> 5) * 2^26 + (lo >> 6)) * 2^-53
+ * NNADQ draws nothing: its records do not depend on seed, draw or the ids.
+ *
+ * Three launches whatever num_tensors is (a minimum / maximum pass over tiles of "quant_tile"
+ * elements, a header pass, the encode pass over the same tiles), no atomics, no host round trip:
+ * asynchronous on `stream`. The result depends on the inputs and the arguments alone. The
+ * accumulator and its state are not touched; nothing outside the records is written. A call's tile
+ * partials live in the context: calls on one context are ordered by their stream.
+ * A non-finite input element latches FEDAVG_FLAG_INPUT_NAN (fedavg_check reports
+ * FEDAVG_ERR_NAN_INPUT); the records of such a call are unspecified but stay inside their buffers.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad codec; a NULL table; num_tensors < 1 or >
+ * 2^20; a negative count; a NULL or misaligned input or record; QSGD: level outside [1, 255]; NNADQ:
+ * a weight that is not finite and > 0; more than 2^31 - 1 tiles), FEDAVG_ERR_STATE (an open dynamic
+ * wave).
+ */
+int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const void* const* in_ptrs /* [T], device */,
+                            const int64_t* numels /* [T], host */,
+                            const uint32_t* tensor_ids /* [T], host, or NULL: 0 .. T - 1 */,
+                            int32_t num_tensors, void* const* record_ptrs /* [T], device */,
+                            int32_t level, double weight, uint64_t seed, uint32_t draw, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
