@@ -22,11 +22,8 @@ LIB_PATH = LIB_DIR / LIB_NAME
 SOURCES = [CSRC / "fedavg_kernels.hip", CSRC / "personalized_kernels.hip", CSRC / "robust_kernels.hip",
            CSRC / "krum_kernels.hip", CSRC / "point_kernels.hip", CSRC / "clip_kernels.hip", CSRC / "trust_kernels.hip",
            CSRC / "opt_kernels.hip", CSRC / "sparse_kernels.hip", CSRC / "route_kernels.hip", CSRC / "quant_kernels.hip",
-           CSRC / "host_pack.cpp", CSRC / "sharded_comm.cpp", CSRC / "multi_device.cpp"]
-HEADERS = [REPO_DIR / "include" / "fedavg_hip.h", CSRC / "exact_div.h", CSRC / "rccl_bind.h",
-           CSRC / "robust_internal.h", CSRC / "krum_internal.h", CSRC / "point_internal.h", CSRC / "clip_internal.h",
-           CSRC / "trust_internal.h", CSRC / "opt_internal.h", CSRC / "sparse_internal.h", CSRC / "route_internal.h",
-           CSRC / "quant_internal.h"]
+           CSRC / "call_tables.cpp", CSRC / "host_pack.cpp", CSRC / "sharded_comm.cpp", CSRC / "multi_device.cpp"]
+HEADERS = [REPO_DIR / "include" / "fedavg_hip.h", *sorted(CSRC.glob("*.h"))]
 # C++ clients of the ABI alone (no Python, no torch), built next to the library
 EXAMPLES = {"c_abi_round": REPO_DIR / "examples" / "c_abi_round.cpp",
             "multi_device_round": REPO_DIR / "examples" / "multi_device_round.cpp",

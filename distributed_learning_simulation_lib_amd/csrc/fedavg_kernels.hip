@@ -40,15 +40,7 @@
 
 #include "../../include/fedavg_hip.h"
 #include "exact_div.h"
-#include "robust_internal.h"
-#include "krum_internal.h"
-#include "point_internal.h"
-#include "clip_internal.h"
-#include "sparse_internal.h"
-#include "route_internal.h"
-#include "quant_internal.h"
-#include "trust_internal.h"
-#include "opt_internal.h"
+#include "internal.h"
 
 namespace {
 
@@ -2248,23 +2240,9 @@ struct fedavg_ctx {
   size_t qtab_last_bytes = 0;                // table bytes of the last QSGD launch
   hipEvent_t aux_done = nullptr;  // the last upload out of aux_host finished
   bool aux_used = false;
-  // per-context state of the robust rules (robust_kernels.hip: tile table, table staging)
-  void* robust = nullptr;
-  // per-context state of the pairwise distances (krum_kernels.hip: chunk table, workspace)
-  void* krum = nullptr;
-  // per-context state of the distances to a point (point_kernels.hip: chunk table, workspace)
-  void* point = nullptr;
-  // per-context state of the fold about a point (clip_kernels.hip: tile table, table staging)
-  void* clip = nullptr;
-  // per-context state of the moments about a point (trust_kernels.hip: chunk table, workspace)
-  void* trust = nullptr;
-  // per-context state of the server optimiser step (opt_kernels.hip: tile table, table staging)
-  void* opt = nullptr;
-  // per-context state of the sparse delta fold (sparse_kernels.hip: tile table, table staging,
-  // the index-violation word)
-  void* sparse = nullptr;
-  // per-context state of the broadcast encoder (quant_kernels.hip: table staging, tile partials)
-  void* quant = nullptr;
+  // per-context state of the side modules (<module>_kernels.hip: span table, table ring, workspace),
+  // created by a module's first call and released through kSideModules
+  void* side_state[FEDAVG_MODULES] = {};
   // the dynamic wave (fedavg_dyn_*): its host-coherent control block and row table, the device
   // mirror words, a private stream (the caller's stream stays free for the work producing the
   // arrivals) and the per-segment totals of the published rows
@@ -3011,6 +2989,33 @@ int out_kind_of(int32_t out_dtype) {
 
 extern "C" __attribute__((visibility("hidden"))) int32_t fedavg_internal_pers_constant(const char* name, int64_t* out);
 
+namespace {
+
+// What the context calls of a side module, indexed by fedavg_module.
+struct SideModule {
+  int32_t (*constant)(const char* name, int64_t* out);
+  void (*release)(int32_t device, void* state);  // NULL: no per-context state
+};
+const SideModule kSideModules[FEDAVG_MODULES] = {
+    {fedavg_internal_robust_constant, fedavg_internal_robust_release},
+    {fedavg_internal_krum_constant, fedavg_internal_krum_release},
+    {fedavg_internal_point_constant, fedavg_internal_point_release},
+    {fedavg_internal_clip_constant, fedavg_internal_clip_release},
+    {fedavg_internal_trust_constant, fedavg_internal_trust_release},
+    {fedavg_internal_opt_constant, fedavg_internal_opt_release},
+    {fedavg_internal_sparse_constant, fedavg_internal_sparse_release},
+    {fedavg_internal_route_constant, nullptr},
+    {fedavg_internal_quant_constant, fedavg_internal_quant_release},
+};
+
+bool side_constant(const char* name, int64_t* v) {
+  for (const SideModule& m : kSideModules)
+    if (m.constant(name, v) == FEDAVG_OK) return true;
+  return false;
+}
+
+}  // namespace
+
 extern "C" {
 
 int32_t fedavg_abi_version(void) { return FEDAVG_ABI_VERSION; }
@@ -3035,24 +3040,7 @@ int32_t fedavg_kernel_constant(const char* name, int64_t* out) {
   else if (n == "nnadq_header") v = kNnadqHeader;
   else if (n.rfind("pers_", 0) == 0) {
     if (fedavg_internal_pers_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("robust_", 0) == 0 || n.rfind("mam_", 0) == 0) {
-    if (fedavg_internal_robust_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("krum_", 0) == 0) {
-    if (fedavg_internal_krum_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("point_", 0) == 0) {
-    if (fedavg_internal_point_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("clip_", 0) == 0) {
-    if (fedavg_internal_clip_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("trust_", 0) == 0) {
-    if (fedavg_internal_trust_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("opt_", 0) == 0) {
-    if (fedavg_internal_opt_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("sparse_", 0) == 0) {
-    if (fedavg_internal_sparse_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("route_", 0) == 0) {
-    if (fedavg_internal_route_constant(name, &v) != FEDAVG_OK) v = -1;
-  } else if (n.rfind("quant_", 0) == 0) {
-    if (fedavg_internal_quant_constant(name, &v) != FEDAVG_OK) v = -1;
+  } else if (side_constant(name, &v)) {
   } else {
     const auto dsep = n.rfind('_');
     const std::string key = dsep == std::string::npos ? n : n.substr(0, dsep);
@@ -3281,14 +3269,8 @@ int32_t fedavg_ctx_destroy(fedavg_ctx* c) {
   if (c->aux_host) (void)hipHostFree(c->aux_host);
   if (c->aux_dev) (void)hipFree(c->aux_dev);
   if (c->aux_done) (void)hipEventDestroy(c->aux_done);
-  if (c->robust) fedavg_internal_robust_release(c->device, c->robust);
-  if (c->krum) fedavg_internal_krum_release(c->device, c->krum);
-  if (c->point) fedavg_internal_point_release(c->device, c->point);
-  if (c->clip) fedavg_internal_clip_release(c->device, c->clip);
-  if (c->trust) fedavg_internal_trust_release(c->device, c->trust);
-  if (c->opt) fedavg_internal_opt_release(c->device, c->opt);
-  if (c->sparse) fedavg_internal_sparse_release(c->device, c->sparse);
-  if (c->quant) fedavg_internal_quant_release(c->device, c->quant);
+  for (int m = 0; m < FEDAVG_MODULES; ++m)
+    if (c->side_state[m] && kSideModules[m].release) kSideModules[m].release(c->device, c->side_state[m]);
   delete c;
   return FEDAVG_OK;
 }
@@ -3501,49 +3483,12 @@ int32_t fedavg_internal_robust_view(fedavg_ctx* c, fedavg_robust_view* out) {
   out->seg_numel = c->seg_numel.data();
   out->d_flag = c->d_flag;
   out->busy = c->dyn.active ? 1 : 0;
-  out->state = &c->robust;
   return FEDAVG_OK;
 }
 
-int32_t fedavg_internal_krum_slot(fedavg_ctx* c, void*** slot) {
+int32_t fedavg_internal_module_slot(fedavg_ctx* c, int32_t module, void*** slot) {
   FEDAVG_RET(check_ctx(c));
-  *slot = &c->krum;
-  return FEDAVG_OK;
-}
-
-int32_t fedavg_internal_point_slot(fedavg_ctx* c, void*** slot) {
-  FEDAVG_RET(check_ctx(c));
-  *slot = &c->point;
-  return FEDAVG_OK;
-}
-
-int32_t fedavg_internal_clip_slot(fedavg_ctx* c, void*** slot) {
-  FEDAVG_RET(check_ctx(c));
-  *slot = &c->clip;
-  return FEDAVG_OK;
-}
-
-int32_t fedavg_internal_trust_slot(fedavg_ctx* c, void*** slot) {
-  FEDAVG_RET(check_ctx(c));
-  *slot = &c->trust;
-  return FEDAVG_OK;
-}
-
-int32_t fedavg_internal_opt_slot(fedavg_ctx* c, void*** slot) {
-  FEDAVG_RET(check_ctx(c));
-  *slot = &c->opt;
-  return FEDAVG_OK;
-}
-
-int32_t fedavg_internal_sparse_slot(fedavg_ctx* c, void*** slot) {
-  FEDAVG_RET(check_ctx(c));
-  *slot = &c->sparse;
-  return FEDAVG_OK;
-}
-
-int32_t fedavg_internal_quant_slot(fedavg_ctx* c, void*** slot) {
-  FEDAVG_RET(check_ctx(c));
-  *slot = &c->quant;
+  *slot = &c->side_state[module];
   return FEDAVG_OK;
 }
 

@@ -37,7 +37,8 @@
 #include <string>
 #include <vector>
 
-#include "krum_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -56,14 +57,9 @@ constexpr int kKrumStride = kKrumBlock + 2;
 static_assert(kKrumChunk % kKrumTile == 0 && kKrumBlocksPerSide * kKrumBlocksPerSide == kKrumThreads, "geometry");
 static_assert(kKrumStride % 2 == 0, "16-byte aligned rows");
 
-struct KChunk {
-  int32_t seg;
-  int32_t count;  // elements in this chunk (kKrumChunk except at a segment's end)
-  int64_t start;  // first element, relative to the segment
-};
 
 struct KArgs {
-  const KChunk* chunks;
+  const Span* chunks;
   const void* const* ptrs;  // [n][num_segments], every entry non-NULL
   double* ws;               // [block pairs][chunks][kKrumPairs]
   uint32_t* flag;
@@ -72,79 +68,6 @@ struct KArgs {
   int32_t num_chunks;
   int32_t pad_;
 };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-struct bf16_t {
-  uint16_t bits;
-};
-
-#define KRUM_AS_GLOBAL __attribute__((address_space(1)))
-#define KRUM_AS_CONST __attribute__((address_space(4)))
-
-// A client's 16 staged bytes -> fp64 values, exactly.
-template <typename T>
-struct KFormat;
-template <>
-struct KFormat<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float(raw[i]));
-  }
-};
-template <>
-struct KFormat<__half> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint32_t h = (raw[i / 2] >> (16 * (i % 2))) & 0xffffu;
-    return static_cast<double>(__half2float(__ushort_as_half(static_cast<unsigned short>(h))));
-  }
-};
-template <>
-struct KFormat<bf16_t> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float((raw[i / 2] >> (16 * (i % 2))) << 16));
-  }
-};
-template <>
-struct KFormat<double> {
-  static constexpr int N = 2;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint64_t lo = raw[2 * i], hi = raw[2 * i + 1];
-    return __longlong_as_double(static_cast<long long>(lo | (hi << 32)));
-  }
-};
-
-// The 16 bytes element by element: only elements below `have` are read (a chunk's last vector at
-// a segment's end, or client storage that is not 16-byte aligned).
-template <typename T>
-__device__ __forceinline__ u32x4 krum_load_guarded(const void* base, int64_t elem, int have) {
-  constexpr int N = KFormat<T>::N;
-  u32x4 raw = {0u, 0u, 0u, 0u};
-  if constexpr (sizeof(T) == 2) {
-    const uint16_t KRUM_AS_GLOBAL* p = (const uint16_t KRUM_AS_GLOBAL*)base + elem;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) raw[i / 2] |= static_cast<uint32_t>(p[i]) << (16 * (i % 2));
-    }
-  } else {
-    constexpr int W = sizeof(T) / 4;  // 32-bit words per element
-    const uint32_t KRUM_AS_GLOBAL* p = (const uint32_t KRUM_AS_GLOBAL*)base + elem * W;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) raw[i * W + w] = p[i * W + w];
-      }
-    }
-  }
-  return raw;
-}
-
-__device__ __forceinline__ void krum_raise_flag(uint32_t* flag, int word) {
-  __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // Block pair index of (I, J), I <= J, with NB blocks per side: row-major over the upper triangle.
 __host__ __device__ __forceinline__ int krum_block_pair(int I, int J, int NB) {
@@ -156,7 +79,7 @@ __host__ __device__ __forceinline__ int krum_block_pair(int I, int J, int NB) {
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kKrumThreads) void krum_chunk_kernel(KArgs a) {
-  using F = KFormat<T>;
+  using F = Format<T>;
   constexpr int N = F::N;
   constexpr int kVecs = kKrumTile / N;                           // 16-byte vectors per client per step
   constexpr int kLoads = kKrumBlock * kVecs / kKrumThreads;      // vectors per lane per step and side
@@ -166,7 +89,7 @@ __global__ __launch_bounds__(kKrumThreads) void krum_chunk_kernel(KArgs a) {
   __shared__ const void* sptr[2 * kKrumBlock];
 
   const int t = static_cast<int>(threadIdx.x);
-  const KChunk KRUM_AS_CONST* cp = (const KChunk KRUM_AS_CONST*)(a.chunks + blockIdx.x);
+  const Span FEDAVG_AS_CONST* cp = (const Span FEDAVG_AS_CONST*)(a.chunks + blockIdx.x);
   const int32_t seg = cp->seg;
   const int32_t count = cp->count;
   const int64_t start = cp->start;
@@ -227,10 +150,10 @@ __global__ __launch_bounds__(kKrumThreads) void krum_chunk_kernel(KArgs a) {
           u32x4 r = {0u, 0u, 0u, 0u};
           if (p != nullptr && have > 0) {
             if (have >= N && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-              const u32x4 KRUM_AS_GLOBAL* q = (const u32x4 KRUM_AS_GLOBAL*)((const T KRUM_AS_GLOBAL*)p + (start + e0));
+              const u32x4 FEDAVG_AS_GLOBAL* q = (const u32x4 FEDAVG_AS_GLOBAL*)((const T FEDAVG_AS_GLOBAL*)p + (start + e0));
               r = __builtin_nontemporal_load(q);
             } else {
-              r = krum_load_guarded<T>(p, start + e0, have);
+              r = load_guarded<T>(p, start + e0, have);
             }
           }
           raw[side][k] = r;
@@ -303,7 +226,7 @@ __global__ __launch_bounds__(kKrumThreads) void krum_chunk_kernel(KArgs a) {
       *reinterpret_cast<f64x2*>(w + r * kKrumBlock + 2) = hi;
     }
   }
-  if (__ballot(nan_in) != 0ull && (t & 63) == 0) krum_raise_flag(a.flag, 2);
+  if (__ballot(nan_in) != 0ull && (t & 63) == 0) raise_flag(a.flag, 2);
 }
 
 // One lane per (i, j), i <= j: the pair's chunk partials added in ascending chunk order, the
@@ -326,64 +249,38 @@ __global__ __launch_bounds__(kKrumThreads) void krum_reduce_kernel(const double*
   for (int c = 0; c < num_chunks; ++c) s += p[static_cast<int64_t>(c) * kKrumPairs];
   out[static_cast<int64_t>(i) * n + j] = s;
   out[static_cast<int64_t>(j) * n + i] = s;
-  if (s != s) krum_raise_flag(flag, 0);  // inf - inf in some element (or a NaN input, flagged at the load too)
+  if (s != s) raise_flag(flag, 0);  // inf - inf in some element (or a NaN input, flagged at the load too)
 }
 
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 struct KrumState {
-  KChunk* d_chunks = nullptr;
+  Span* d_chunks = nullptr;
   int64_t num_chunks = 0;
   double* ws = nullptr;  // grown lazily to the largest client count seen
   size_t ws_bytes = 0;
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's pointer table
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launch that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;  // a call's tables: the client pointers
+  ~KrumState() {
+    ring.release();
+    if (d_chunks) (void)hipFree(d_chunks);
+    if (ws) (void)hipFree(ws);
+  }
 };
 
-#define KRUM_HIP_TRY(expr)                                                                            \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
 int32_t ensure_state(const fedavg_robust_view& v, void** slot, KrumState** out) {
-  if (*slot != nullptr) {
-    *out = static_cast<KrumState*>(*slot);
-    return FEDAVG_OK;
-  }
-  std::vector<KChunk> chunks;
-  for (int32_t t = 0; t < v.num_segments; ++t) {
-    for (int64_t s = 0; s < v.seg_numel[t]; s += kKrumChunk) {
-      const int64_t left = v.seg_numel[t] - s;
-      chunks.push_back(KChunk{t, static_cast<int32_t>(left < kKrumChunk ? left : kKrumChunk), s});
+  if (*slot == nullptr) {
+    KrumState* st = new KrumState();
+    int32_t r = span_table(v.seg_numel, v.num_segments, kKrumChunk, "distance launch", "krum chunk table", &st->d_chunks,
+                           &st->num_chunks);
+    if (r == FEDAVG_OK) r = hip_status("krum chunk table", st->ring.create());
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
     }
+    *slot = st;
   }
-  if (chunks.empty() || chunks.size() > 0x7fffffffull) return invalid("layout too large for one distance launch");
-  KrumState* st = new KrumState();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_chunks), sizeof(KChunk) * chunks.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_chunks, chunks.data(), sizeof(KChunk) * chunks.size(), hipMemcpyHostToDevice);
-  for (auto& sl : st->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    if (st->d_chunks) (void)hipFree(st->d_chunks);
-    for (auto& sl : st->slots)
-      if (sl.done) (void)hipEventDestroy(sl.done);
-    delete st;
-    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("krum chunk table: ") + hipGetErrorString(e)).c_str());
-  }
-  st->num_chunks = static_cast<int64_t>(chunks.size());
-  *slot = st;
-  *out = st;
+  *out = static_cast<KrumState*>(*slot);
   return FEDAVG_OK;
 }
 
@@ -397,27 +294,18 @@ int32_t fedavg_internal_krum_constant(const char* name, int64_t* out) {
   else if (n == "krum_reg") *out = kKrumReg;
   else if (n == "krum_threads") *out = kKrumThreads;
   else if (n == "krum_max_clients") *out = kKrumMaxClients;
-  else if (n == "krum_ae_f32") *out = KFormat<float>::N;
-  else if (n == "krum_ae_f16") *out = KFormat<__half>::N;
-  else if (n == "krum_ae_bf16") *out = KFormat<bf16_t>::N;
-  else if (n == "krum_ae_f64") *out = KFormat<double>::N;
+  else if (n == "krum_ae_f32") *out = Format<float>::N;
+  else if (n == "krum_ae_f16") *out = Format<__half>::N;
+  else if (n == "krum_ae_bf16") *out = Format<bf16_t>::N;
+  else if (n == "krum_ae_f64") *out = Format<double>::N;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
 
 void fedavg_internal_krum_release(int32_t device, void* state) {
-  KrumState* st = static_cast<KrumState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  if (st->d_chunks) (void)hipFree(st->d_chunks);
-  if (st->ws) (void)hipFree(st->ws);
-  delete st;
+  delete static_cast<KrumState*>(state);
 }
 
 extern "C" int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
@@ -426,7 +314,7 @@ extern "C" int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* cl
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_krum_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_KRUM, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
@@ -448,7 +336,7 @@ extern "C" int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* cl
     if (reinterpret_cast<uintptr_t>(p) % elem_bytes != 0) return invalid("client tensor not aligned to its element size");
   }
 
-  KRUM_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   KrumState* st = nullptr;
   const int32_t re = ensure_state(v, slot, &st);
   if (re != FEDAVG_OK) return re;
@@ -458,29 +346,19 @@ extern "C" int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* cl
   const int num_bp = NB * (NB + 1) / 2;
   const size_t ws_bytes = sizeof(double) * static_cast<size_t>(num_bp) * static_cast<size_t>(st->num_chunks) * kKrumPairs;
   if (st->ws_bytes < ws_bytes) {
-    if (st->ws) KRUM_HIP_TRY(hipFree(st->ws));  // synchronises with the launches that used it
+    if (st->ws) FEDAVG_TRY_HIP(hipFree(st->ws));  // synchronises with the launches that used it
     st->ws = nullptr;
     st->ws_bytes = 0;
-    KRUM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->ws), ws_bytes));
+    FEDAVG_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&st->ws), ws_bytes));
     st->ws_bytes = ws_bytes;
   }
 
   const size_t bytes = sizeof(void*) * entries;
-  KrumState::Slot& sl = st->slots[st->next];
-  st->next ^= 1;
-  if (sl.used) KRUM_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's table
-  if (sl.cap < bytes) {
-    if (sl.host) KRUM_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) KRUM_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    KRUM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    KRUM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.acquire(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   std::memcpy(sl.host, client_ptrs, bytes);
-  KRUM_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
 
   KArgs a;
   a.chunks = st->d_chunks;
@@ -499,12 +377,10 @@ extern "C" int32_t fedavg_pairwise_sqdist(fedavg_ctx* ctx, const void* const* cl
     case FEDAVG_BF16: hipLaunchKernelGGL(krum_chunk_kernel<bf16_t>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(krum_chunk_kernel<double>, grid, block, 0, s, a); break;
   }
-  KRUM_HIP_TRY(hipGetLastError());
+  FEDAVG_TRY_HIP(hipGetLastError());
   const unsigned cells = static_cast<unsigned>(num_clients) * static_cast<unsigned>(num_clients);
   hipLaunchKernelGGL(krum_reduce_kernel, dim3((cells + kKrumThreads - 1) / kKrumThreads), block, 0, s, st->ws,
                      static_cast<int32_t>(st->num_chunks), num_clients, out, v.d_flag);
-  KRUM_HIP_TRY(hipGetLastError());
-  KRUM_HIP_TRY(hipEventRecord(sl.done, s));
-  sl.used = true;
-  return FEDAVG_OK;
+  FEDAVG_TRY_HIP(hipGetLastError());
+  return st->ring.retire(sl, s);
 }

@@ -39,7 +39,8 @@
 #include <string>
 #include <vector>
 
-#include "opt_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 #ifndef FEDAVG_OPT_STATE_EARLY
 #define FEDAVG_OPT_STATE_EARLY 0
@@ -51,14 +52,9 @@ constexpr int kOptThreads = 256;  // lanes per workgroup
 constexpr int kOptTile = 2048;    // elements per workgroup: 8 per lane for every client dtype
 constexpr int kOptMaxClients = FEDAVG_POINT_MAX_CLIENTS;
 
-struct OTile {
-  int32_t seg;
-  int32_t count;  // elements in this tile (kOptTile except at a segment's end)
-  int64_t start;  // first element, relative to the segment
-};
 
 struct OArgs {
-  const OTile* tiles;
+  const Span* tiles;
   const void* const* ptrs;      // [n][num_segments], every entry non-NULL
   const double* const* point;   // [num_segments]
   const double* const* m_in;    // [num_segments]
@@ -75,86 +71,15 @@ struct OArgs {
   int32_t mode;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-struct bf16_t {
-  uint16_t bits;
-};
-
-#define OPT_AS_GLOBAL __attribute__((address_space(1)))
-#define OPT_AS_CONST __attribute__((address_space(4)))
-
-// A client's 16 staged bytes -> fp64 values, exactly.
-template <typename T>
-struct OFormat;
-template <>
-struct OFormat<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float(raw[i]));
-  }
-};
-template <>
-struct OFormat<__half> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint32_t h = (raw[i / 2] >> (16 * (i % 2))) & 0xffffu;
-    return static_cast<double>(__half2float(__ushort_as_half(static_cast<unsigned short>(h))));
-  }
-};
-template <>
-struct OFormat<bf16_t> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float((raw[i / 2] >> (16 * (i % 2))) << 16));
-  }
-};
-template <>
-struct OFormat<double> {
-  static constexpr int N = 2;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint64_t lo = raw[2 * i], hi = raw[2 * i + 1];
-    return __longlong_as_double(static_cast<long long>(lo | (hi << 32)));
-  }
-};
-
-// The 16 bytes element by element: only elements below `have` are read (a tile's last vector at a
-// segment's end, or client storage that is not 16-byte aligned); the rest stay +0.0.
-template <typename T>
-__device__ __forceinline__ u32x4 opt_load_guarded(const void* base, int64_t elem, int have) {
-  constexpr int N = OFormat<T>::N;
-  u32x4 raw = {0u, 0u, 0u, 0u};
-  if constexpr (sizeof(T) == 2) {
-    const uint16_t OPT_AS_GLOBAL* p = (const uint16_t OPT_AS_GLOBAL*)base + elem;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) raw[i / 2] |= static_cast<uint32_t>(p[i]) << (16 * (i % 2));
-    }
-  } else {
-    constexpr int W = sizeof(T) / 4;  // 32-bit words per element
-    const uint32_t OPT_AS_GLOBAL* p = (const uint32_t OPT_AS_GLOBAL*)base + elem * W;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) raw[i * W + w] = p[i * W + w];
-      }
-    }
-  }
-  return raw;
-}
-
 // N fp64 values of a point or moment segment from base[elem ..]: `vec` says 16-byte loads are
 // aligned and inside; otherwise only elements below `have` are read and the rest stay +0.0.
 template <int N>
 __device__ __forceinline__ void opt_load_f64(const double* base, int64_t elem, double (&dst)[N], int have, bool vec) {
-  const double OPT_AS_GLOBAL* q = (const double OPT_AS_GLOBAL*)base + elem;
+  const double FEDAVG_AS_GLOBAL* q = (const double FEDAVG_AS_GLOBAL*)base + elem;
   if (vec) {
 #pragma unroll
     for (int i = 0; i < N; i += 2) {
-      const f64x2 v = *(const f64x2 OPT_AS_GLOBAL*)(q + i);
+      const f64x2 v = *(const f64x2 FEDAVG_AS_GLOBAL*)(q + i);
       dst[i] = v[0];
       dst[i + 1] = v[1];
     }
@@ -167,23 +92,23 @@ __device__ __forceinline__ void opt_load_f64(const double* base, int64_t elem, d
 // One vector's N results to out[elem ..]: `vec` says the 16-byte stores are aligned and inside.
 template <typename O, int N>
 __device__ __forceinline__ void opt_store(void* base, int64_t elem, const double (&r)[N], int have, bool vec) {
-  O OPT_AS_GLOBAL* o = (O OPT_AS_GLOBAL*)base + elem;
+  O FEDAVG_AS_GLOBAL* o = (O FEDAVG_AS_GLOBAL*)base + elem;
   if (vec) {
     if constexpr (sizeof(O) == 8) {
 #pragma unroll
       for (int i = 0; i < N; i += 2) {
         const f64x2 v = {r[i], r[i + 1]};
-        *(f64x2 OPT_AS_GLOBAL*)(o + i) = v;
+        *(f64x2 FEDAVG_AS_GLOBAL*)(o + i) = v;
       }
     } else if constexpr (N == 2) {  // elem is even and the base 16-byte aligned: an aligned 8-byte store
       const f32x2 v = {static_cast<float>(r[0]), static_cast<float>(r[1])};
-      *(f32x2 OPT_AS_GLOBAL*)o = v;
+      *(f32x2 FEDAVG_AS_GLOBAL*)o = v;
     } else {
 #pragma unroll
       for (int i = 0; i < N; i += 4) {
         const f32x4 v = {static_cast<float>(r[i]), static_cast<float>(r[i + 1]), static_cast<float>(r[i + 2]),
                          static_cast<float>(r[i + 3])};
-        *(f32x4 OPT_AS_GLOBAL*)(o + i) = v;
+        *(f32x4 FEDAVG_AS_GLOBAL*)(o + i) = v;
       }
     }
   } else {
@@ -192,10 +117,6 @@ __device__ __forceinline__ void opt_store(void* base, int64_t elem, const double
       if (i < have) o[i] = static_cast<O>(r[i]);
     }
   }
-}
-
-__device__ __forceinline__ void opt_raise_flag(uint32_t* flag, int word) {
-  __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // The correctly rounded fp64 square root: RN(sqrt(x)) for every x (sqrt(-0) = -0, x < 0 = NaN),
@@ -243,7 +164,7 @@ __device__ __forceinline__ void opt_epilogue(const OArgs& a, double delta, doubl
 // ---------------------------------------------------------------------------------------
 template <typename T, typename O>
 __global__ __launch_bounds__(kOptThreads) void opt_step_kernel(OArgs a) {
-  using F = OFormat<T>;
+  using F = Format<T>;
   constexpr int N = F::N;
   constexpr int K = kOptTile / (N * kOptThreads);  // 16-byte vectors per lane and client
   static_assert(K >= 1 && K * N * kOptThreads == kOptTile && N % 2 == 0, "tile geometry");
@@ -253,7 +174,7 @@ __global__ __launch_bounds__(kOptThreads) void opt_step_kernel(OArgs a) {
 
   const int t = static_cast<int>(threadIdx.x);
   const int lane = t & 63;
-  const OTile OPT_AS_CONST* tp = (const OTile OPT_AS_CONST*)(a.tiles + blockIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
   const int32_t seg = tp->seg;
   const int32_t count = tp->count;
   const int64_t start = tp->start;
@@ -320,10 +241,10 @@ __global__ __launch_bounds__(kOptThreads) void opt_step_kernel(OArgs a) {
       u32x4 r = {0u, 0u, 0u, 0u};
       if (have > 0) {
         if (have >= N && vec) {
-          const u32x4 OPT_AS_GLOBAL* q = (const u32x4 OPT_AS_GLOBAL*)((const T OPT_AS_GLOBAL*)p + (start + e0));
+          const u32x4 FEDAVG_AS_GLOBAL* q = (const u32x4 FEDAVG_AS_GLOBAL*)((const T FEDAVG_AS_GLOBAL*)p + (start + e0));
           r = __builtin_nontemporal_load(q);
         } else {
-          r = opt_load_guarded<T>(p, start + e0, have);
+          r = load_guarded<T>(p, start + e0, have);
         }
       }
       dst[k] = r;
@@ -395,64 +316,37 @@ __global__ __launch_bounds__(kOptThreads) void opt_step_kernel(OArgs a) {
       if (adaptive) opt_store<double, N>(pvo, start + e0, vn, have, have >= N && pvo_vec);
     }
   }
-  if (__ballot(nan_in) != 0ull && lane == 0) opt_raise_flag(a.flag, 2);
-  if (__ballot(nan_acc) != 0ull && lane == 0) opt_raise_flag(a.flag, 0);
-  if (__ballot(nan_out) != 0ull && lane == 0) opt_raise_flag(a.flag, 1);
+  if (__ballot(nan_in) != 0ull && lane == 0) raise_flag(a.flag, 2);
+  if (__ballot(nan_acc) != 0ull && lane == 0) raise_flag(a.flag, 0);
+  if (__ballot(nan_out) != 0ull && lane == 0) raise_flag(a.flag, 1);
 }
 
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 struct OptState {
-  OTile* d_tiles = nullptr;
+  Span* d_tiles = nullptr;
   int64_t num_tiles = 0;
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's tables (clients, point, moments, outs, coefficients)
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launch that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;  // a call's tables: clients, point, moments, outs, coefficients
+  ~OptState() {
+    ring.release();
+    if (d_tiles) (void)hipFree(d_tiles);
+  }
 };
 
-#define OPT_HIP_TRY(expr)                                                                             \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
 int32_t ensure_state(const fedavg_robust_view& v, void** slot, OptState** out) {
-  if (*slot != nullptr) {
-    *out = static_cast<OptState*>(*slot);
-    return FEDAVG_OK;
-  }
-  std::vector<OTile> tiles;
-  for (int32_t t = 0; t < v.num_segments; ++t) {
-    for (int64_t s = 0; s < v.seg_numel[t]; s += kOptTile) {
-      const int64_t left = v.seg_numel[t] - s;
-      tiles.push_back(OTile{t, static_cast<int32_t>(left < kOptTile ? left : kOptTile), s});
+  if (*slot == nullptr) {
+    OptState* st = new OptState();
+    int32_t r = span_table(v.seg_numel, v.num_segments, kOptTile, "server optimiser step", "opt tile table", &st->d_tiles,
+                           &st->num_tiles);
+    if (r == FEDAVG_OK) r = hip_status("opt tile table", st->ring.create());
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
     }
+    *slot = st;
   }
-  if (tiles.empty() || tiles.size() > 0x7fffffffull) return invalid("layout too large for one server optimiser step");
-  OptState* st = new OptState();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_tiles), sizeof(OTile) * tiles.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_tiles, tiles.data(), sizeof(OTile) * tiles.size(), hipMemcpyHostToDevice);
-  for (auto& sl : st->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    if (st->d_tiles) (void)hipFree(st->d_tiles);
-    for (auto& sl : st->slots)
-      if (sl.done) (void)hipEventDestroy(sl.done);
-    delete st;
-    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("opt tile table: ") + hipGetErrorString(e)).c_str());
-  }
-  st->num_tiles = static_cast<int64_t>(tiles.size());
-  *slot = st;
-  *out = st;
+  *out = static_cast<OptState*>(*slot);
   return FEDAVG_OK;
 }
 
@@ -473,26 +367,18 @@ int32_t fedavg_internal_opt_constant(const char* name, int64_t* out) {
   if (n == "opt_tile") *out = kOptTile;
   else if (n == "opt_threads") *out = kOptThreads;
   else if (n == "opt_max_clients") *out = kOptMaxClients;
-  else if (n == "opt_ae_f32") *out = OFormat<float>::N;
-  else if (n == "opt_ae_f16") *out = OFormat<__half>::N;
-  else if (n == "opt_ae_bf16") *out = OFormat<bf16_t>::N;
-  else if (n == "opt_ae_f64") *out = OFormat<double>::N;
+  else if (n == "opt_ae_f32") *out = Format<float>::N;
+  else if (n == "opt_ae_f16") *out = Format<__half>::N;
+  else if (n == "opt_ae_bf16") *out = Format<bf16_t>::N;
+  else if (n == "opt_ae_f64") *out = Format<double>::N;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
 
 void fedavg_internal_opt_release(int32_t device, void* state) {
-  OptState* st = static_cast<OptState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  if (st->d_tiles) (void)hipFree(st->d_tiles);
-  delete st;
+  delete static_cast<OptState*>(state);
 }
 
 extern "C" int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
@@ -506,7 +392,7 @@ extern "C" int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* cl
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_opt_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_OPT, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
@@ -564,7 +450,7 @@ extern "C" int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* cl
     }
   }
 
-  OPT_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   OptState* st = nullptr;
   const int32_t re = ensure_state(v, slot, &st);
   if (re != FEDAVG_OK) return re;
@@ -576,19 +462,9 @@ extern "C" int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* cl
   const size_t seg_bytes = sizeof(void*) * static_cast<size_t>(T);
   const size_t coef_bytes = sizeof(double) * static_cast<size_t>(num_clients);
   const size_t bytes = client_bytes + 6 * seg_bytes + coef_bytes;
-  OptState::Slot& sl = st->slots[st->next];
-  st->next ^= 1;
-  if (sl.used) OPT_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's tables
-  if (sl.cap < bytes) {
-    if (sl.host) OPT_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) OPT_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    OPT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    OPT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.acquire(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   const void* const seg_tables[6] = {point_ptrs, m_in, adaptive ? v_in : nullptr, m_out, adaptive ? v_out : nullptr,
                                      out_ptrs};
   std::memcpy(sl.host, client_ptrs, client_bytes);
@@ -598,7 +474,7 @@ extern "C" int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* cl
     else std::memset(dst, 0, seg_bytes);
   }
   std::memcpy(sl.host + client_bytes + 6 * seg_bytes, coefficients, coef_bytes);
-  OPT_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
 
   char* const segs = sl.dev + client_bytes;
   OArgs a;
@@ -626,8 +502,6 @@ extern "C" int32_t fedavg_server_opt_step(fedavg_ctx* ctx, const void* const* cl
   const dim3 block(kOptThreads);
   if (out_dtype == FEDAVG_F32) launch<float>(in_dtype, grid, block, s, a);
   else launch<double>(in_dtype, grid, block, s, a);
-  OPT_HIP_TRY(hipGetLastError());
-  OPT_HIP_TRY(hipEventRecord(sl.done, s));
-  sl.used = true;
-  return FEDAVG_OK;
+  FEDAVG_TRY_HIP(hipGetLastError());
+  return st->ring.retire(sl, s);
 }

@@ -41,7 +41,8 @@
 #include <string>
 #include <vector>
 
-#include "point_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -56,14 +57,9 @@ static_assert(kPointThreads % 64 == 0 && kPointBatch <= kPointThreads, "geometry
 static_assert(kPointRedClients * (kPointThreads / kPointRedClients) == kPointThreads &&
               kPointRedTile % (kPointThreads / kPointRedClients) == 0, "reduce geometry");
 
-struct PChunk {
-  int32_t seg;
-  int32_t count;  // elements in this chunk (kPointChunk except at a segment's end)
-  int64_t start;  // first element, relative to the segment
-};
 
 struct PArgs {
-  const PChunk* chunks;
+  const Span* chunks;
   const void* const* ptrs;      // [n][num_segments], every entry non-NULL
   const double* const* point;   // [num_segments], or NULL: the origin
   double* ws;                   // [chunks][n]
@@ -72,85 +68,12 @@ struct PArgs {
   int32_t n;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-struct bf16_t {
-  uint16_t bits;
-};
-
-#define POINT_AS_GLOBAL __attribute__((address_space(1)))
-#define POINT_AS_CONST __attribute__((address_space(4)))
-
-// A client's 16 staged bytes -> fp64 values, exactly.
-template <typename T>
-struct PFormat;
-template <>
-struct PFormat<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float(raw[i]));
-  }
-};
-template <>
-struct PFormat<__half> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint32_t h = (raw[i / 2] >> (16 * (i % 2))) & 0xffffu;
-    return static_cast<double>(__half2float(__ushort_as_half(static_cast<unsigned short>(h))));
-  }
-};
-template <>
-struct PFormat<bf16_t> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float((raw[i / 2] >> (16 * (i % 2))) << 16));
-  }
-};
-template <>
-struct PFormat<double> {
-  static constexpr int N = 2;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint64_t lo = raw[2 * i], hi = raw[2 * i + 1];
-    return __longlong_as_double(static_cast<long long>(lo | (hi << 32)));
-  }
-};
-
-// The 16 bytes element by element: only elements below `have` are read (a chunk's last vector at
-// a segment's end, or client storage that is not 16-byte aligned); the rest stay +0.0.
-template <typename T>
-__device__ __forceinline__ u32x4 point_load_guarded(const void* base, int64_t elem, int have) {
-  constexpr int N = PFormat<T>::N;
-  u32x4 raw = {0u, 0u, 0u, 0u};
-  if constexpr (sizeof(T) == 2) {
-    const uint16_t POINT_AS_GLOBAL* p = (const uint16_t POINT_AS_GLOBAL*)base + elem;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) raw[i / 2] |= static_cast<uint32_t>(p[i]) << (16 * (i % 2));
-    }
-  } else {
-    constexpr int W = sizeof(T) / 4;  // 32-bit words per element
-    const uint32_t POINT_AS_GLOBAL* p = (const uint32_t POINT_AS_GLOBAL*)base + elem * W;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) raw[i * W + w] = p[i * W + w];
-      }
-    }
-  }
-  return raw;
-}
-
-__device__ __forceinline__ void point_raise_flag(uint32_t* flag, int word) {
-  __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // ---------------------------------------------------------------------------------------
 // the chunk kernel: blockIdx.x = chunk
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kPointThreads) void point_chunk_kernel(PArgs a) {
-  using F = PFormat<T>;
+  using F = Format<T>;
   constexpr int N = F::N;
   constexpr int K = kPointChunk / (N * kPointThreads);  // 16-byte vectors per lane and client
   static_assert(K >= 1 && K * N * kPointThreads == kPointChunk && N % 2 == 0, "chunk geometry");
@@ -160,7 +83,7 @@ __global__ __launch_bounds__(kPointThreads) void point_chunk_kernel(PArgs a) {
 
   const int t = static_cast<int>(threadIdx.x);
   const int lane = t & 63, wave = t >> 6;
-  const PChunk POINT_AS_CONST* cp = (const PChunk POINT_AS_CONST*)(a.chunks + blockIdx.x);
+  const Span FEDAVG_AS_CONST* cp = (const Span FEDAVG_AS_CONST*)(a.chunks + blockIdx.x);
   const int32_t seg = cp->seg;
   const int32_t count = cp->count;
   const int64_t start = cp->start;
@@ -181,11 +104,11 @@ __global__ __launch_bounds__(kPointThreads) void point_chunk_kernel(PArgs a) {
 #pragma unroll
     for (int i = 0; i < N; ++i) z[k][i] = 0.0;
     if (pz != nullptr && have > 0) {
-      const double POINT_AS_GLOBAL* q = (const double POINT_AS_GLOBAL*)pz + (start + e0);
+      const double FEDAVG_AS_GLOBAL* q = (const double FEDAVG_AS_GLOBAL*)pz + (start + e0);
       if (have >= N && pz_vec) {  // start and e0 are even: 16-byte aligned with the segment
 #pragma unroll
         for (int i = 0; i < N; i += 2) {
-          const f64x2 v = *(const f64x2 POINT_AS_GLOBAL*)(q + i);
+          const f64x2 v = *(const f64x2 FEDAVG_AS_GLOBAL*)(q + i);
           z[k][i] = v[0];
           z[k][i + 1] = v[1];
         }
@@ -211,10 +134,10 @@ __global__ __launch_bounds__(kPointThreads) void point_chunk_kernel(PArgs a) {
       u32x4 r = {0u, 0u, 0u, 0u};
       if (have > 0) {
         if (have >= N && vec) {
-          const u32x4 POINT_AS_GLOBAL* q = (const u32x4 POINT_AS_GLOBAL*)((const T POINT_AS_GLOBAL*)p + (start + e0));
+          const u32x4 FEDAVG_AS_GLOBAL* q = (const u32x4 FEDAVG_AS_GLOBAL*)((const T FEDAVG_AS_GLOBAL*)p + (start + e0));
           r = __builtin_nontemporal_load(q);
         } else {
-          r = point_load_guarded<T>(p, start + e0, have);
+          r = load_guarded<T>(p, start + e0, have);
         }
       }
       dst[k] = r;
@@ -263,7 +186,7 @@ __global__ __launch_bounds__(kPointThreads) void point_chunk_kernel(PArgs a) {
       reduce(bufb, c + 1);
     }
   }
-  if (__ballot(nan_in) != 0ull && lane == 0) point_raise_flag(a.flag, 2);
+  if (__ballot(nan_in) != 0ull && lane == 0) raise_flag(a.flag, 2);
 }
 
 // A workgroup owns kPointRedClients clients: it stages kPointRedTile chunk partials of each in LDS
@@ -303,7 +226,7 @@ __global__ __launch_bounds__(kPointThreads) void point_reduce_kernel(const doubl
   }
   if (t < kPointRedClients && client < n) {
     out[client] = s;
-    if (s != s) point_raise_flag(flag, 0);  // inf - inf in some element (or a NaN input, flagged at the load too)
+    if (s != s) raise_flag(flag, 0);  // inf - inf in some element (or a NaN input, flagged at the load too)
   }
 }
 
@@ -311,57 +234,31 @@ __global__ __launch_bounds__(kPointThreads) void point_reduce_kernel(const doubl
 // host side
 // ---------------------------------------------------------------------------------------
 struct PointState {
-  PChunk* d_chunks = nullptr;
+  Span* d_chunks = nullptr;
   int64_t num_chunks = 0;
   double* ws = nullptr;  // grown lazily to the largest client count seen
   size_t ws_bytes = 0;
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's pointer tables (clients, then the point)
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launch that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;  // a call's tables: clients, then the point
+  ~PointState() {
+    ring.release();
+    if (d_chunks) (void)hipFree(d_chunks);
+    if (ws) (void)hipFree(ws);
+  }
 };
 
-#define POINT_HIP_TRY(expr)                                                                           \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
 int32_t ensure_state(const fedavg_robust_view& v, void** slot, PointState** out) {
-  if (*slot != nullptr) {
-    *out = static_cast<PointState*>(*slot);
-    return FEDAVG_OK;
-  }
-  std::vector<PChunk> chunks;
-  for (int32_t t = 0; t < v.num_segments; ++t) {
-    for (int64_t s = 0; s < v.seg_numel[t]; s += kPointChunk) {
-      const int64_t left = v.seg_numel[t] - s;
-      chunks.push_back(PChunk{t, static_cast<int32_t>(left < kPointChunk ? left : kPointChunk), s});
+  if (*slot == nullptr) {
+    PointState* st = new PointState();
+    int32_t r = span_table(v.seg_numel, v.num_segments, kPointChunk, "distance launch", "point chunk table", &st->d_chunks,
+                           &st->num_chunks);
+    if (r == FEDAVG_OK) r = hip_status("point chunk table", st->ring.create());
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
     }
+    *slot = st;
   }
-  if (chunks.empty() || chunks.size() > 0x7fffffffull) return invalid("layout too large for one distance launch");
-  PointState* st = new PointState();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_chunks), sizeof(PChunk) * chunks.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_chunks, chunks.data(), sizeof(PChunk) * chunks.size(), hipMemcpyHostToDevice);
-  for (auto& sl : st->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    if (st->d_chunks) (void)hipFree(st->d_chunks);
-    for (auto& sl : st->slots)
-      if (sl.done) (void)hipEventDestroy(sl.done);
-    delete st;
-    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("point chunk table: ") + hipGetErrorString(e)).c_str());
-  }
-  st->num_chunks = static_cast<int64_t>(chunks.size());
-  *slot = st;
-  *out = st;
+  *out = static_cast<PointState*>(*slot);
   return FEDAVG_OK;
 }
 
@@ -373,27 +270,18 @@ int32_t fedavg_internal_point_constant(const char* name, int64_t* out) {
   else if (n == "point_threads") *out = kPointThreads;
   else if (n == "point_batch") *out = kPointBatch;
   else if (n == "point_max_clients") *out = kPointMaxClients;
-  else if (n == "point_ae_f32") *out = PFormat<float>::N;
-  else if (n == "point_ae_f16") *out = PFormat<__half>::N;
-  else if (n == "point_ae_bf16") *out = PFormat<bf16_t>::N;
-  else if (n == "point_ae_f64") *out = PFormat<double>::N;
+  else if (n == "point_ae_f32") *out = Format<float>::N;
+  else if (n == "point_ae_f16") *out = Format<__half>::N;
+  else if (n == "point_ae_bf16") *out = Format<bf16_t>::N;
+  else if (n == "point_ae_f64") *out = Format<double>::N;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
 
 void fedavg_internal_point_release(int32_t device, void* state) {
-  PointState* st = static_cast<PointState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  if (st->d_chunks) (void)hipFree(st->d_chunks);
-  if (st->ws) (void)hipFree(st->ws);
-  delete st;
+  delete static_cast<PointState*>(state);
 }
 
 extern "C" int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
@@ -403,7 +291,7 @@ extern "C" int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* cl
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_point_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_POINT, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
@@ -431,7 +319,7 @@ extern "C" int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* cl
     }
   }
 
-  POINT_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   PointState* st = nullptr;
   const int32_t re = ensure_state(v, slot, &st);
   if (re != FEDAVG_OK) return re;
@@ -439,32 +327,22 @@ extern "C" int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* cl
 
   const size_t ws_bytes = sizeof(double) * static_cast<size_t>(st->num_chunks) * static_cast<size_t>(num_clients);
   if (st->ws_bytes < ws_bytes) {
-    if (st->ws) POINT_HIP_TRY(hipFree(st->ws));  // synchronises with the launches that used it
+    if (st->ws) FEDAVG_TRY_HIP(hipFree(st->ws));  // synchronises with the launches that used it
     st->ws = nullptr;
     st->ws_bytes = 0;
-    POINT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->ws), ws_bytes));
+    FEDAVG_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&st->ws), ws_bytes));
     st->ws_bytes = ws_bytes;
   }
 
   // the call's pointer tables: [n][T] client pointers, then [T] point pointers
   const size_t client_bytes = sizeof(void*) * entries;
   const size_t bytes = client_bytes + (point_ptrs != nullptr ? sizeof(void*) * static_cast<size_t>(T) : 0);
-  PointState::Slot& sl = st->slots[st->next];
-  st->next ^= 1;
-  if (sl.used) POINT_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's table
-  if (sl.cap < bytes) {
-    if (sl.host) POINT_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) POINT_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    POINT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    POINT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.acquire(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   std::memcpy(sl.host, client_ptrs, client_bytes);
   if (point_ptrs != nullptr) std::memcpy(sl.host + client_bytes, point_ptrs, bytes - client_bytes);
-  POINT_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
 
   PArgs a;
   a.chunks = st->d_chunks;
@@ -482,12 +360,10 @@ extern "C" int32_t fedavg_sqdist_to_point(fedavg_ctx* ctx, const void* const* cl
     case FEDAVG_BF16: hipLaunchKernelGGL(point_chunk_kernel<bf16_t>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(point_chunk_kernel<double>, grid, block, 0, s, a); break;
   }
-  POINT_HIP_TRY(hipGetLastError());
+  FEDAVG_TRY_HIP(hipGetLastError());
   const unsigned groups = (static_cast<unsigned>(num_clients) + kPointRedClients - 1) / kPointRedClients;
   hipLaunchKernelGGL(point_reduce_kernel, dim3(groups), block, 0, s, st->ws, static_cast<int32_t>(st->num_chunks),
                      num_clients, out, v.d_flag);
-  POINT_HIP_TRY(hipGetLastError());
-  POINT_HIP_TRY(hipEventRecord(sl.done, s));
-  sl.used = true;
-  return FEDAVG_OK;
+  FEDAVG_TRY_HIP(hipGetLastError());
+  return st->ring.retire(sl, s);
 }

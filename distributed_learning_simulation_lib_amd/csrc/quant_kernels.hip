@@ -36,7 +36,8 @@
 #include <string>
 #include <vector>
 
-#include "quant_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -46,14 +47,8 @@ constexpr int kQTile = kQThreads * kQPerLane;   // elements per workgroup
 constexpr int kQMaxTensors = 1 << 20;
 static_assert(kQTile % 128 == 0, "tile starts are multiples of 128 elements");
 
-struct QTile {
-  int32_t seg;
-  int32_t count;  // elements in this tile (kQTile except at a tensor's end)
-  int64_t start;  // first element, relative to the tensor
-};
-
 struct QArgs {
-  const QTile* tiles;
+  const Span* tiles;
   const void* const* in;      // [T]; NULL only where numel == 0
   uint8_t* const* rec;        // [T], 16-byte aligned
   const int64_t* numel;       // [T]
@@ -65,12 +60,6 @@ struct QArgs {
   uint32_t key0, key1, draw;
   int32_t level;
 };
-
-#define Q_AS_GLOBAL __attribute__((address_space(1)))
-typedef uint32_t q_u32x4 __attribute__((ext_vector_type(4)));
-typedef float q_f32x4 __attribute__((ext_vector_type(4)));
-typedef double q_f64x2 __attribute__((ext_vector_type(2)));
-#define Q_AS_CONST __attribute__((address_space(4)))
 
 template <typename F>
 struct QT;
@@ -105,10 +94,6 @@ __device__ __forceinline__ F q_unkey(uint64_t key) {
   return QT<F>::value((k & QT<F>::kSign) ? static_cast<U>(k ^ QT<F>::kSign) : static_cast<U>(~k));
 }
 
-__device__ __forceinline__ void q_raise(uint32_t* word) {
-  __hip_atomic_store(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // minimum and maximum over the workgroup; the result is valid in thread 0
 __device__ __forceinline__ void q_block_minmax(uint64_t& mn, uint64_t& mx, uint64_t* smn, uint64_t* smx) {
 #pragma unroll
@@ -141,10 +126,10 @@ __global__ __launch_bounds__(kQThreads) void quant_minmax_kernel(QArgs a) {
   using U = typename QT<F>::U;
   __shared__ uint64_t smn[kQThreads / 64], smx[kQThreads / 64];
   const int t = static_cast<int>(threadIdx.x);
-  const QTile Q_AS_CONST* tp = (const QTile Q_AS_CONST*)(a.tiles + blockIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
   const int32_t seg = tp->seg;
   const int32_t count = tp->count;
-  const U Q_AS_GLOBAL* p = (const U Q_AS_GLOBAL*)a.in[seg] + tp->start;
+  const U FEDAVG_AS_GLOBAL* p = (const U FEDAVG_AS_GLOBAL*)a.in[seg] + tp->start;
   uint64_t mn = ~0ull, mx = 0ull;
   bool bad = false;
 #pragma unroll
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(kQThreads) void quant_minmax_kernel(QArgs a) {
     a.part[2 * static_cast<int64_t>(blockIdx.x)] = mn;
     a.part[2 * static_cast<int64_t>(blockIdx.x) + 1] = mx;
   }
-  if (__ballot(bad) != 0ull && (t & 63) == 0) q_raise(a.flag + 2);
+  if (__ballot(bad) != 0ull && (t & 63) == 0) raise_flag(a.flag, 2);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -313,17 +298,17 @@ __device__ __forceinline__ void q_load16(const F* src, int have, F* x);
 template <>
 __device__ __forceinline__ void q_load16<float>(const float* src, int have, float* x) {
   if (have == kQPerLane && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
-    const q_f32x4 Q_AS_GLOBAL* p = (const q_f32x4 Q_AS_GLOBAL*)src;
+    const f32x4 FEDAVG_AS_GLOBAL* p = (const f32x4 FEDAVG_AS_GLOBAL*)src;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const q_f32x4 v = p[j];
+      const f32x4 v = p[j];
       x[4 * j] = v.x;
       x[4 * j + 1] = v.y;
       x[4 * j + 2] = v.z;
       x[4 * j + 3] = v.w;
     }
   } else {
-    const float Q_AS_GLOBAL* p = (const float Q_AS_GLOBAL*)src;
+    const float FEDAVG_AS_GLOBAL* p = (const float FEDAVG_AS_GLOBAL*)src;
 #pragma unroll
     for (int i = 0; i < kQPerLane; ++i) x[i] = i < have ? p[i] : 0.0f;
   }
@@ -331,15 +316,15 @@ __device__ __forceinline__ void q_load16<float>(const float* src, int have, floa
 template <>
 __device__ __forceinline__ void q_load16<double>(const double* src, int have, double* x) {
   if (have == kQPerLane && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
-    const q_f64x2 Q_AS_GLOBAL* p = (const q_f64x2 Q_AS_GLOBAL*)src;
+    const f64x2 FEDAVG_AS_GLOBAL* p = (const f64x2 FEDAVG_AS_GLOBAL*)src;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const q_f64x2 v = p[j];
+      const f64x2 v = p[j];
       x[2 * j] = v.x;
       x[2 * j + 1] = v.y;
     }
   } else {
-    const double Q_AS_GLOBAL* p = (const double Q_AS_GLOBAL*)src;
+    const double FEDAVG_AS_GLOBAL* p = (const double FEDAVG_AS_GLOBAL*)src;
 #pragma unroll
     for (int i = 0; i < kQPerLane; ++i) x[i] = i < have ? p[i] : 0.0;
   }
@@ -351,7 +336,7 @@ __device__ __forceinline__ void q_load16<double>(const double* src, int have, do
 template <typename F, bool NNADQ>
 __global__ __launch_bounds__(kQThreads) void quant_encode_kernel(QArgs a) {
   const int t = static_cast<int>(threadIdx.x);
-  const QTile Q_AS_CONST* tp = (const QTile Q_AS_CONST*)(a.tiles + blockIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
   const int32_t seg = tp->seg;
   const int32_t count = tp->count;
   const int64_t start = tp->start;
@@ -403,8 +388,8 @@ __global__ __launch_bounds__(kQThreads) void quant_encode_kernel(QArgs a) {
     }
     const int64_t sign_area = (((n + 7) >> 3) + 15) & ~static_cast<int64_t>(15);
     const int64_t sb = e0 >> 3;
-    if (sb < sign_area) *(uint16_t Q_AS_GLOBAL*)(rec + 16 + area + sb) = static_cast<uint16_t>(sign);
-    if (e0 < area) *(q_u32x4 Q_AS_GLOBAL*)(rec + 16 + e0) = q_u32x4{pk[0], pk[1], pk[2], pk[3]};
+    if (sb < sign_area) *(uint16_t FEDAVG_AS_GLOBAL*)(rec + 16 + area + sb) = static_cast<uint16_t>(sign);
+    if (e0 < area) *(u32x4 FEDAVG_AS_GLOBAL*)(rec + 16 + e0) = u32x4{pk[0], pk[1], pk[2], pk[3]};
   } else {
     const ulonglong2 h0 = *reinterpret_cast<const ulonglong2*>(rec);
     const ulonglong2 h1 = *reinterpret_cast<const ulonglong2*>(rec + 16);
@@ -420,7 +405,7 @@ __global__ __launch_bounds__(kQThreads) void quant_encode_kernel(QArgs a) {
       const uint32_t b = (live && i < have) ? q_byte<F>(c, top) : 0u;
       pk[i >> 2] |= b << (8 * (i & 3));
     }
-    if (e0 < area) *(q_u32x4 Q_AS_GLOBAL*)(rec + 32 + e0) = q_u32x4{pk[0], pk[1], pk[2], pk[3]};
+    if (e0 < area) *(u32x4 FEDAVG_AS_GLOBAL*)(rec + 32 + e0) = u32x4{pk[0], pk[1], pk[2], pk[3]};
   }
 }
 
@@ -430,45 +415,20 @@ __global__ __launch_bounds__(kQThreads) void quant_encode_kernel(QArgs a) {
 struct QuantState {
   uint64_t* d_part = nullptr;  // the tile partials of the call in flight
   size_t part_cap = 0;         // in tiles
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's tables
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launches that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
-};
-
-#define Q_HIP_TRY(expr)                                                                               \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
-void free_state(QuantState* st) {
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
+  TableRing ring;
+  ~QuantState() {
+    ring.release();
+    if (d_part) (void)hipFree(d_part);
   }
-  if (st->d_part) (void)hipFree(st->d_part);
-  delete st;
-}
+};
 
 int32_t ensure_state(void** slot, QuantState** out) {
   if (*slot == nullptr) {
     QuantState* st = new QuantState();
-    hipError_t e = hipSuccess;
-    for (auto& sl : st->slots)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-      free_state(st);
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("quant state: ") + hipGetErrorString(e)).c_str());
+    const int32_t r = hip_status("quant state", st->ring.create());
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
     }
     *slot = st;
   }
@@ -503,10 +463,9 @@ int32_t fedavg_internal_quant_constant(const char* name, int64_t* out) {
 }
 
 void fedavg_internal_quant_release(int32_t device, void* state) {
-  QuantState* st = static_cast<QuantState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  free_state(st);
+  delete static_cast<QuantState*>(state);
 }
 
 extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const void* const* in_ptrs,
@@ -517,7 +476,7 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_quant_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_QUANT, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (codec != FEDAVG_QSGD_F32 && codec != FEDAVG_QSGD_F64 && codec != FEDAVG_NNADQ_F32 && codec != FEDAVG_NNADQ_F64)
@@ -545,24 +504,24 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
   }
   if (num_tiles > 0x7fffffffull) return invalid("layout too large for one encode call");
 
-  Q_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   QuantState* st = nullptr;
   const int32_t re = ensure_state(slot, &st);
   if (re != FEDAVG_OK) return re;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
   if (st->part_cap < num_tiles) {  // hipFree waits for the device: no launch still reads the old buffer
-    if (st->d_part) Q_HIP_TRY(hipFree(st->d_part));
+    if (st->d_part) FEDAVG_TRY_HIP(hipFree(st->d_part));
     st->d_part = nullptr;
     st->part_cap = 0;
     const size_t cap = num_tiles * 2 < 1024 ? 1024 : num_tiles * 2;
-    Q_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->d_part), cap * 2 * sizeof(uint64_t)));
+    FEDAVG_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&st->d_part), cap * 2 * sizeof(uint64_t)));
     st->part_cap = cap;
   }
 
   // the call's tables: the tiles, [T] input pointers, [T] record pointers, [T] element counts,
   // [T] stream ids, [T + 1] first tile of every tensor
-  const size_t tile_bytes = align16(sizeof(QTile) * num_tiles);
+  const size_t tile_bytes = align16(sizeof(Span) * num_tiles);
   const size_t ptr_bytes = align16(sizeof(void*) * static_cast<size_t>(T));
   const size_t id_bytes = align16(sizeof(uint32_t) * static_cast<size_t>(T));
   const size_t first_bytes = align16(sizeof(int32_t) * (static_cast<size_t>(T) + 1));
@@ -570,21 +529,11 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
                o_first = o_id + id_bytes;
   const size_t bytes = o_first + first_bytes;
   // `next` advances only once work that reads this slot has been enqueued and its event recorded
-  QuantState::Slot& sl = st->slots[st->next];
-  if (sl.used) Q_HIP_TRY(hipEventSynchronize(sl.done));
-  sl.used = false;
-  if (sl.cap < bytes) {
-    if (sl.host) Q_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) Q_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    Q_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    Q_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.peek(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   std::memset(sl.host, 0, bytes);
-  QTile* const h_tiles = reinterpret_cast<QTile*>(sl.host);
+  Span* const h_tiles = reinterpret_cast<Span*>(sl.host);
   int32_t* const h_first = reinterpret_cast<int32_t*>(sl.host + o_first);
   uint32_t* const h_ids = reinterpret_cast<uint32_t*>(sl.host + o_id);
   size_t k = 0;
@@ -593,17 +542,17 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
     h_ids[t] = tensor_ids ? tensor_ids[t] : static_cast<uint32_t>(t);
     for (int64_t b = 0; b < numels[t]; b += kQTile) {
       const int64_t left = numels[t] - b;
-      h_tiles[k++] = QTile{t, static_cast<int32_t>(left < kQTile ? left : kQTile), b};
+      h_tiles[k++] = Span{t, static_cast<int32_t>(left < kQTile ? left : kQTile), b};
     }
   }
   h_first[T] = static_cast<int32_t>(k);
   std::memcpy(sl.host + o_in, in_ptrs, sizeof(void*) * static_cast<size_t>(T));
   std::memcpy(sl.host + o_rec, record_ptrs, sizeof(void*) * static_cast<size_t>(T));
   std::memcpy(sl.host + o_numel, numels, sizeof(int64_t) * static_cast<size_t>(T));
-  Q_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
 
   QArgs a;
-  a.tiles = reinterpret_cast<const QTile*>(sl.dev);
+  a.tiles = reinterpret_cast<const Span*>(sl.dev);
   a.in = reinterpret_cast<const void* const*>(sl.dev + o_in);
   a.rec = reinterpret_cast<uint8_t* const*>(sl.dev + o_rec);
   a.numel = reinterpret_cast<const int64_t*>(sl.dev + o_numel);
@@ -619,14 +568,7 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
   if (f64) launch_all<double>(nnadq, static_cast<unsigned>(num_tiles), static_cast<unsigned>(T), s, a);
   else launch_all<float>(nnadq, static_cast<unsigned>(num_tiles), static_cast<unsigned>(T), s, a);
   hipError_t e = hipGetLastError();
-  // the copy is on the stream whatever became of the launches: the slot is guarded either way
-  const hipError_t er = hipEventRecord(sl.done, s);
-  if (er == hipSuccess) {
-    sl.used = true;
-    st->next ^= 1;
-  } else {
-    (void)hipStreamSynchronize(s);  // no event to wait for: leave the slot idle before it is reused
-  }
+  const hipError_t er = st->ring.commit(sl, s);
   if (e == hipSuccess) e = er;
   if (e != hipSuccess)
     return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("quant encode launch: ") + hipGetErrorString(e)).c_str());

@@ -33,7 +33,8 @@
 #include <utility>
 #include <vector>
 
-#include "robust_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -41,11 +42,6 @@ constexpr int kRobustLanes = 64;                           // one wave per workg
 constexpr int kRobustTile = 512;                           // elements per tile (all dtypes)
 constexpr int kRobustMaxClients = FEDAVG_ROBUST_MAX_CLIENTS;  // the widest network
 
-struct RTile {
-  int32_t seg;
-  int32_t count;  // elements in this tile (kRobustTile except at a segment's end)
-  int64_t start;  // first element, relative to the segment
-};
 
 struct RSeg {      // one segment of a call
   void* out;
@@ -57,23 +53,13 @@ struct RSeg {      // one segment of a call
 };
 
 struct RArgs {
-  const RTile* tiles;
+  const Span* tiles;
   const RSeg* segs;
   const void* const* ptrs;  // per segment n dense client pointers (missing clients compacted away)
   uint32_t* flag;
   int32_t out_f32;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-struct bf16_t {
-  uint16_t bits;
-};
-
-#define ROBUST_AS_GLOBAL __attribute__((address_space(1)))
-#define ROBUST_AS_CONST __attribute__((address_space(4)))
 // the loop bodies below are lambdas over a compile-time index; they must be inlined for the
 // register arrays they touch to stay registers
 #define ROBUST_INLINE __attribute__((always_inline))
@@ -188,9 +174,9 @@ struct KeyLimits<uint64_t> {
 };
 
 template <typename T>
-struct Format;
+struct KeyFormat;
 template <>
-struct Format<float> {
+struct KeyFormat<float> {
   using Key = uint32_t;
   static constexpr int N = 4;
   template <int J>
@@ -199,7 +185,7 @@ struct Format<float> {
   }
 };
 template <>
-struct Format<__half> {
+struct KeyFormat<__half> {
   using Key = uint32_t;
   static constexpr int N = 8;
   template <int J>
@@ -209,7 +195,7 @@ struct Format<__half> {
   }
 };
 template <>
-struct Format<bf16_t> {
+struct KeyFormat<bf16_t> {
   using Key = uint32_t;
   static constexpr int N = 8;
   template <int J>
@@ -219,7 +205,7 @@ struct Format<bf16_t> {
   }
 };
 template <>
-struct Format<double> {
+struct KeyFormat<double> {
   using Key = uint64_t;
   static constexpr int N = 2;
   template <int J>
@@ -229,56 +215,26 @@ struct Format<double> {
   }
 };
 
-// The lane's 16 bytes of one client, element by element: only elements below `have` are read
-// (a segment's last vector, or a segment whose storage is not 16-byte aligned).
-template <typename T>
-__device__ __forceinline__ u32x4 load_guarded(const void* base, int64_t elem, int have) {
-  constexpr int N = Format<T>::N;
-  u32x4 raw = {0u, 0u, 0u, 0u};
-  if constexpr (sizeof(T) == 2) {
-    const uint16_t ROBUST_AS_GLOBAL* p = (const uint16_t ROBUST_AS_GLOBAL*)base + elem;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) raw[i / 2] |= static_cast<uint32_t>(p[i]) << (16 * (i % 2));
-    }
-  } else {
-    constexpr int W = sizeof(T) / 4;  // 32-bit words per element
-    const uint32_t ROBUST_AS_GLOBAL* p = (const uint32_t ROBUST_AS_GLOBAL*)base + elem * W;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) raw[i * W + w] = p[i * W + w];
-      }
-    }
-  }
-  return raw;
-}
-
-__device__ __forceinline__ void raise_flag(uint32_t* flag, int word) {
-  __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 template <typename O, int N>
 __device__ __forceinline__ void store_results(void* out, int64_t elem, const double (&res)[N], bool vec, int have) {
-  O ROBUST_AS_GLOBAL* o = (O ROBUST_AS_GLOBAL*)out + elem;
+  O FEDAVG_AS_GLOBAL* o = (O FEDAVG_AS_GLOBAL*)out + elem;
   if (vec) {
     if constexpr (sizeof(O) == 8) {
 #pragma unroll
       for (int i = 0; i < N; i += 2) {
         f64x2 v = {res[i], res[i + 1]};
-        __builtin_nontemporal_store(v, (f64x2 ROBUST_AS_GLOBAL*)(o + i));
+        __builtin_nontemporal_store(v, (f64x2 FEDAVG_AS_GLOBAL*)(o + i));
       }
     } else if constexpr (N >= 4) {
 #pragma unroll
       for (int i = 0; i < N; i += 4) {
         f32x4 v = {static_cast<float>(res[i]), static_cast<float>(res[i + 1]), static_cast<float>(res[i + 2]),
                    static_cast<float>(res[i + 3])};
-        __builtin_nontemporal_store(v, (f32x4 ROBUST_AS_GLOBAL*)(o + i));
+        __builtin_nontemporal_store(v, (f32x4 FEDAVG_AS_GLOBAL*)(o + i));
       }
     } else {
       f32x2 v = {static_cast<float>(res[0]), static_cast<float>(res[1])};
-      __builtin_nontemporal_store(v, (f32x2 ROBUST_AS_GLOBAL*)o);
+      __builtin_nontemporal_store(v, (f32x2 FEDAVG_AS_GLOBAL*)o);
     }
   } else {
 #pragma unroll
@@ -293,7 +249,7 @@ __device__ __forceinline__ void store_results(void* out, int64_t elem, const dou
 // ---------------------------------------------------------------------------------------
 template <typename T, int NPAD>
 __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes))) void robust_tile_kernel(RArgs a) {
-  using F = Format<T>;
+  using F = KeyFormat<T>;
   using Key = typename F::Key;
   using L = KeyLimits<Key>;
   constexpr int N = F::N;
@@ -301,16 +257,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes
   static_assert(kRobustTile % kPass == 0, "tile geometry");
 
   // wave-uniform descriptors through the constant address space (scalar loads)
-  const RTile ROBUST_AS_CONST* tp = (const RTile ROBUST_AS_CONST*)(a.tiles + blockIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
   const int32_t seg = tp->seg;
   const int32_t count = tp->count;
   const int64_t start = tp->start;
-  const RSeg ROBUST_AS_CONST* sp = (const RSeg ROBUST_AS_CONST*)(a.segs + seg);
+  const RSeg FEDAVG_AS_CONST* sp = (const RSeg FEDAVG_AS_CONST*)(a.segs + seg);
   void* const out = sp->out;
   const int32_t n = sp->n;
   const int32_t k = sp->k;
   const bool seg_vec = sp->vec != 0;
-  const void* const ROBUST_AS_CONST* ptrs = (const void* const ROBUST_AS_CONST*)(a.ptrs + sp->first);
+  const void* const FEDAVG_AS_CONST* ptrs = (const void* const FEDAVG_AS_CONST*)(a.ptrs + sp->first);
   const double divisor = static_cast<double>(n - 2 * k);
   const int lane = static_cast<int>(threadIdx.x);
 
@@ -340,8 +296,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes
         static_for<kBatch>([&](auto I) ROBUST_INLINE {
           constexpr int j = b * kBatch + decltype(I)::value;
           if (j < n) {
-            const u32x4 ROBUST_AS_GLOBAL* p =
-                (const u32x4 ROBUST_AS_GLOBAL*)((const T ROBUST_AS_GLOBAL*)ptrs[j] + elem);
+            const u32x4 FEDAVG_AS_GLOBAL* p =
+                (const u32x4 FEDAVG_AS_GLOBAL*)((const T FEDAVG_AS_GLOBAL*)ptrs[j] + elem);
             raw[j - b * kBatch] = __builtin_nontemporal_load(p);
           }
         });
@@ -470,7 +426,7 @@ struct Sorted<double> {
 // number of values averaged (1 <= beta <= n).
 template <typename T, int NPAD>
 __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes))) void mam_tile_kernel(RArgs a) {
-  using F = Format<T>;
+  using F = KeyFormat<T>;
   using Key = typename F::Key;
   using L = KeyLimits<Key>;
   using S = Sorted<T>;
@@ -478,16 +434,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes
   constexpr int kPass = kRobustLanes * N;
   static_assert(kRobustTile % kPass == 0, "tile geometry");
 
-  const RTile ROBUST_AS_CONST* tp = (const RTile ROBUST_AS_CONST*)(a.tiles + blockIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
   const int32_t seg = tp->seg;
   const int32_t count = tp->count;
   const int64_t start = tp->start;
-  const RSeg ROBUST_AS_CONST* sp = (const RSeg ROBUST_AS_CONST*)(a.segs + seg);
+  const RSeg FEDAVG_AS_CONST* sp = (const RSeg FEDAVG_AS_CONST*)(a.segs + seg);
   void* const out = sp->out;
   const int32_t n = sp->n;
   const int32_t beta = sp->k;
   const bool seg_vec = sp->vec != 0;
-  const void* const ROBUST_AS_CONST* ptrs = (const void* const ROBUST_AS_CONST*)(a.ptrs + sp->first);
+  const void* const FEDAVG_AS_CONST* ptrs = (const void* const FEDAVG_AS_CONST*)(a.ptrs + sp->first);
   const double divisor = static_cast<double>(beta);
   const int32_t mid = (n - 1) >> 1;  // the lower median's slot
   const int lane = static_cast<int>(threadIdx.x);
@@ -514,8 +470,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes
         static_for<kBatch>([&](auto I) ROBUST_INLINE {
           constexpr int j = b * kBatch + decltype(I)::value;
           if (j < n) {
-            const u32x4 ROBUST_AS_GLOBAL* p =
-                (const u32x4 ROBUST_AS_GLOBAL*)((const T ROBUST_AS_GLOBAL*)ptrs[j] + elem);
+            const u32x4 FEDAVG_AS_GLOBAL* p =
+                (const u32x4 FEDAVG_AS_GLOBAL*)((const T FEDAVG_AS_GLOBAL*)ptrs[j] + elem);
             raw[j - b * kBatch] = __builtin_nontemporal_load(p);
           }
         });
@@ -590,55 +546,28 @@ __global__ __attribute__((amdgpu_flat_work_group_size(kRobustLanes, kRobustLanes
 // host side
 // ---------------------------------------------------------------------------------------
 struct RobustState {
-  RTile* d_tiles = nullptr;
+  Span* d_tiles = nullptr;
   int64_t num_tiles = 0;
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's tables (RSeg[T], then the pointer list)
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launch that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;  // a call's tables: RSeg[T], then the pointer list
+  ~RobustState() {
+    if (d_tiles) (void)hipFree(d_tiles);
+    ring.release();
+  }
 };
 
-#define ROBUST_HIP_TRY(expr)                                                                          \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
-int32_t ensure_state(const fedavg_robust_view& v, RobustState** out) {
-  if (*v.state != nullptr) {
-    *out = static_cast<RobustState*>(*v.state);
-    return FEDAVG_OK;
-  }
-  std::vector<RTile> tiles;
-  for (int32_t t = 0; t < v.num_segments; ++t) {
-    for (int64_t s = 0; s < v.seg_numel[t]; s += kRobustTile) {
-      const int64_t left = v.seg_numel[t] - s;
-      tiles.push_back(RTile{t, static_cast<int32_t>(left < kRobustTile ? left : kRobustTile), s});
+int32_t ensure_state(const fedavg_robust_view& v, void** slot, RobustState** out) {
+  if (*slot == nullptr) {
+    RobustState* st = new RobustState();
+    int32_t r = span_table(v.seg_numel, v.num_segments, kRobustTile, "robust launch", "robust tile table", &st->d_tiles,
+                           &st->num_tiles);
+    if (r == FEDAVG_OK) r = hip_status("robust tile table", st->ring.create());
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
     }
+    *slot = st;
   }
-  if (tiles.size() > 0x7fffffffull) return invalid("layout too large for one robust launch");
-  RobustState* st = new RobustState();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_tiles), sizeof(RTile) * tiles.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_tiles, tiles.data(), sizeof(RTile) * tiles.size(), hipMemcpyHostToDevice);
-  for (auto& sl : st->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    if (st->d_tiles) (void)hipFree(st->d_tiles);
-    for (auto& sl : st->slots)
-      if (sl.done) (void)hipEventDestroy(sl.done);
-    delete st;
-    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("robust tile table: ") + hipGetErrorString(e)).c_str());
-  }
-  st->num_tiles = static_cast<int64_t>(tiles.size());
-  *v.state = st;
-  *out = st;
+  *out = static_cast<RobustState*>(*slot);
   return FEDAVG_OK;
 }
 
@@ -710,37 +639,25 @@ int32_t collect_segments(const fedavg_robust_view& v, const void* const* client_
 
 // The tables go through one of two pinned slots to the device (a slot is reused once the launch
 // that read it has finished); *a is ready for the launch, which the caller records in *slot.
-int32_t upload_tables(const fedavg_robust_view& v, const std::vector<RSeg>& segs, const std::vector<const void*>& list,
-                      int32_t out_dtype, hipStream_t s, RobustState** state, RobustState::Slot** slot, RArgs* a) {
-  ROBUST_HIP_TRY(hipSetDevice(v.device));
+int32_t upload_tables(const fedavg_robust_view& v, void** state_slot, const std::vector<RSeg>& segs,
+                      const std::vector<const void*>& list, int32_t out_dtype, hipStream_t s, RobustState** state,
+                      TableRing::Slot** slot, RArgs* a) {
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   RobustState* st = nullptr;
-  const int32_t rs = ensure_state(v, &st);
-  if (rs != FEDAVG_OK) return rs;
+  FEDAVG_TRY(ensure_state(v, state_slot, &st));
   const size_t seg_bytes = sizeof(RSeg) * segs.size();
   const size_t bytes = seg_bytes + sizeof(void*) * list.size();
-  RobustState::Slot& sl = st->slots[st->next];
-  st->next ^= 1;
-  if (sl.used) ROBUST_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's tables
-  if (sl.cap < bytes) {
-    if (sl.host) ROBUST_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) ROBUST_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    ROBUST_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    ROBUST_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  FEDAVG_TRY(st->ring.acquire(bytes, slot));
+  TableRing::Slot& sl = **slot;
   std::memcpy(sl.host, segs.data(), seg_bytes);
   std::memcpy(sl.host + seg_bytes, list.data(), sizeof(void*) * list.size());
-  ROBUST_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
   a->tiles = st->d_tiles;
   a->segs = reinterpret_cast<const RSeg*>(sl.dev);
   a->ptrs = reinterpret_cast<const void* const*>(sl.dev + seg_bytes);
   a->flag = v.d_flag;
   a->out_f32 = out_dtype == FEDAVG_F32 ? 1 : 0;
   *state = st;
-  *slot = &sl;
   return FEDAVG_OK;
 }
 
@@ -757,32 +674,24 @@ int32_t fedavg_internal_robust_constant(const char* name, int64_t* out) {
   if (n == "robust_tile") *out = kRobustTile;
   else if (n == "robust_lanes") *out = kRobustLanes;
   else if (n == "robust_max_clients") *out = kRobustMaxClients;
-  else if (n == "robust_ae_f32") *out = Format<float>::N;
-  else if (n == "robust_ae_f16") *out = Format<__half>::N;
-  else if (n == "robust_ae_bf16") *out = Format<bf16_t>::N;
-  else if (n == "robust_ae_f64") *out = Format<double>::N;
+  else if (n == "robust_ae_f32") *out = KeyFormat<float>::N;
+  else if (n == "robust_ae_f16") *out = KeyFormat<__half>::N;
+  else if (n == "robust_ae_bf16") *out = KeyFormat<bf16_t>::N;
+  else if (n == "robust_ae_f64") *out = KeyFormat<double>::N;
   else if (n == "mam_tile") *out = kRobustTile;
   else if (n == "mam_lanes") *out = kRobustLanes;
-  else if (n == "mam_ae_f32") *out = Format<float>::N;
-  else if (n == "mam_ae_f16") *out = Format<__half>::N;
-  else if (n == "mam_ae_bf16") *out = Format<bf16_t>::N;
-  else if (n == "mam_ae_f64") *out = Format<double>::N;
+  else if (n == "mam_ae_f32") *out = KeyFormat<float>::N;
+  else if (n == "mam_ae_f16") *out = KeyFormat<__half>::N;
+  else if (n == "mam_ae_bf16") *out = KeyFormat<bf16_t>::N;
+  else if (n == "mam_ae_f64") *out = KeyFormat<double>::N;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
 
 void fedavg_internal_robust_release(int32_t device, void* state) {
-  RobustState* st = static_cast<RobustState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  if (st->d_tiles) (void)hipFree(st->d_tiles);
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  delete st;
+  delete static_cast<RobustState*>(state);
 }
 
 extern "C" int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
@@ -791,6 +700,9 @@ extern "C" int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* c
   fedavg_robust_view v;
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
+  void** slot = nullptr;
+  const int32_t rm = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_ROBUST, &slot);
+  if (rm != FEDAVG_OK) return rm;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
     return invalid("robust aggregation reads dense fp32 / fp16 / bf16 / fp64 tensors (no records)");
@@ -820,9 +732,9 @@ extern "C" int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* c
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   RobustState* st = nullptr;
-  RobustState::Slot* sl = nullptr;
+  TableRing::Slot* sl = nullptr;
   RArgs a;
-  const int32_t ru = upload_tables(v, segs, list, out_dtype, s, &st, &sl, &a);
+  const int32_t ru = upload_tables(v, slot, segs, list, out_dtype, s, &st, &sl, &a);
   if (ru != FEDAVG_OK) return ru;
   const dim3 grid(static_cast<unsigned>(st->num_tiles));
   switch (in_dtype) {
@@ -831,10 +743,8 @@ extern "C" int32_t fedavg_robust_aggregate(fedavg_ctx* ctx, const void* const* c
     case FEDAVG_BF16: launch_npad<bf16_t>(npad, grid, s, a); break;
     default: launch_npad<double>(npad, grid, s, a); break;
   }
-  ROBUST_HIP_TRY(hipGetLastError());
-  ROBUST_HIP_TRY(hipEventRecord(sl->done, s));
-  sl->used = true;
-  return FEDAVG_OK;
+  FEDAVG_TRY_HIP(hipGetLastError());
+  return st->ring.retire(*sl, s);
 }
 
 extern "C" int32_t fedavg_mean_around_median(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
@@ -843,6 +753,9 @@ extern "C" int32_t fedavg_mean_around_median(fedavg_ctx* ctx, const void* const*
   fedavg_robust_view v;
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
+  void** slot = nullptr;
+  const int32_t rm = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_ROBUST, &slot);
+  if (rm != FEDAVG_OK) return rm;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
     return invalid("the mean around the median reads dense fp32 / fp16 / bf16 / fp64 tensors (no records)");
@@ -870,9 +783,9 @@ extern "C" int32_t fedavg_mean_around_median(fedavg_ctx* ctx, const void* const*
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   RobustState* st = nullptr;
-  RobustState::Slot* sl = nullptr;
+  TableRing::Slot* sl = nullptr;
   RArgs a;
-  const int32_t ru = upload_tables(v, segs, list, out_dtype, s, &st, &sl, &a);
+  const int32_t ru = upload_tables(v, slot, segs, list, out_dtype, s, &st, &sl, &a);
   if (ru != FEDAVG_OK) return ru;
   const dim3 grid(static_cast<unsigned>(st->num_tiles));
   switch (in_dtype) {
@@ -881,8 +794,6 @@ extern "C" int32_t fedavg_mean_around_median(fedavg_ctx* ctx, const void* const*
     case FEDAVG_BF16: launch_mam_npad<bf16_t>(npad, grid, s, a); break;
     default: launch_mam_npad<double>(npad, grid, s, a); break;
   }
-  ROBUST_HIP_TRY(hipGetLastError());
-  ROBUST_HIP_TRY(hipEventRecord(sl->done, s));
-  sl->used = true;
-  return FEDAVG_OK;
+  FEDAVG_TRY_HIP(hipGetLastError());
+  return st->ring.retire(*sl, s);
 }

@@ -39,7 +39,8 @@
 #include <string>
 #include <vector>
 
-#include "route_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -82,13 +83,6 @@ struct RArgs {
   int32_t id_blocks;          // workgroups that walk the sent ids in a mixed launch
 };
 
-#define RT_AS_GLOBAL __attribute__((address_space(1)))
-typedef uint32_t rt_u32x4 __attribute__((ext_vector_type(4)));  // one 16-byte load / store
-
-__device__ __forceinline__ void rt_raise(uint32_t* word) {
-  __hip_atomic_store(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // ---------------------------------------------------------------------------------------
 // 1. the map: blockIdx.x * kRtThreads + lane = sent row
 // ---------------------------------------------------------------------------------------
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(kRtThreads) void route_scatter_kernel(RArgs a) {
     if (id >= 0 && id < a.node_space) a.table[id] = static_cast<int32_t>(r);
     else bad = true;
   }
-  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) rt_raise(a.err + 2);
+  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) raise_flag(a.err, 2);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(kRtThreads) void route_rank_kernel(RArgs a) {
       const int64_t id = a.src_ids[r];
       if (id >= 0 && id < a.node_space) dup = a.table[id] != static_cast<int32_t>(r);
     }
-    if (__ballot(dup) != 0ull && lane == 0) rt_raise(a.err + 0);
+    if (__ballot(dup) != 0ull && lane == 0) raise_flag(a.err, 0);
     return;
   }
   const int32_t c = static_cast<int32_t>(blockIdx.x) - a.id_blocks;
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(kRtThreads) void route_rank_kernel(RArgs a) {
     if (row[p] >= 0) a.ws_src[g0 + base + prefix[p]] = row[p];
   }
   if (t == 0) a.chunk_count[c] = total;
-  if (__ballot(disorder) != 0ull && lane == 0) rt_raise(a.err + 1);
+  if (__ballot(disorder) != 0ull && lane == 0) raise_flag(a.err, 1);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(kRtThreads) void route_scan_kernel(RArgs a, int32_t
 // 4. the rows: blockIdx.x = chunk, blockIdx.y = part of the chunk's flat range of units
 // ---------------------------------------------------------------------------------------
 template <typename T, typename I>
-__device__ __forceinline__ void rt_copy(const uint64_t* sptr, T RT_AS_GLOBAL* dst, I u0, I u1, I upr, int t) {
+__device__ __forceinline__ void rt_copy(const uint64_t* sptr, T FEDAVG_AS_GLOBAL* dst, I u0, I u1, I upr, int t) {
   // dst is the chunk's first output row; unit u of the flat range is unit u % upr of hit u / upr
   constexpr int U = 4;
   I u = u0 + static_cast<I>(t);
@@ -213,14 +207,14 @@ __device__ __forceinline__ void rt_copy(const uint64_t* sptr, T RT_AS_GLOBAL* ds
     for (int q = 0; q < U; ++q) {
       const I uu = u + static_cast<I>(q * kRtThreads);
       const I k = uu / upr;
-      v[q] = ((const T RT_AS_GLOBAL*)sptr[k])[uu - k * upr];
+      v[q] = ((const T FEDAVG_AS_GLOBAL*)sptr[k])[uu - k * upr];
     }
 #pragma unroll
     for (int q = 0; q < U; ++q) dst[u + static_cast<I>(q * kRtThreads)] = v[q];
   }
   for (; u < u1; u += static_cast<I>(kRtThreads)) {
     const I k = u / upr;
-    dst[u] = ((const T RT_AS_GLOBAL*)sptr[k])[u - k * upr];
+    dst[u] = ((const T FEDAVG_AS_GLOBAL*)sptr[k])[u - k * upr];
   }
 }
 
@@ -263,28 +257,18 @@ __global__ __launch_bounds__(kRtThreads) void route_gather_kernel(RArgs a) {
     if (static_cast<int64_t>(k) * upr >= u0) a.out_ids[dst0 + k] = a.src_ids[r];
   }
   __syncthreads();
-  T RT_AS_GLOBAL* const dst = (T RT_AS_GLOBAL*)a.out_rows + dst0 * upr;
+  T FEDAVG_AS_GLOBAL* const dst = (T FEDAVG_AS_GLOBAL*)a.out_rows + dst0 * upr;
   if (total <= 0x7fffffffll)
     rt_copy<T, uint32_t>(sptr, dst, static_cast<uint32_t>(u0), static_cast<uint32_t>(u1), static_cast<uint32_t>(upr), t);
   else
     rt_copy<T, int64_t>(sptr, dst, u0, u1, upr, t);
 }
 
+}  // namespace
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-#define RT_HIP_TRY(expr)                                                                              \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
-bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
-
-}  // namespace
 
 struct fedavg_route {
   int32_t device = 0;
@@ -294,14 +278,7 @@ struct fedavg_route {
   uint32_t* d_err = nullptr;   // 3 words, latched by the kernels, cleared by fedavg_route_errors
   char* d_ws = nullptr;        // ws_src, chunk_count, chunk_base of the call in flight
   size_t ws_cap = 0;
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's tables
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launches that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;
 };
 
 int32_t fedavg_internal_route_constant(const char* name, int64_t* out) {
@@ -318,11 +295,7 @@ extern "C" int32_t fedavg_route_destroy(fedavg_route* p) {
   if (p == nullptr) return FEDAVG_OK;
   (void)hipSetDevice(p->device);
   (void)hipDeviceSynchronize();
-  for (auto& sl : p->slots) {
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
+  p->ring.release();
   if (p->d_table) (void)hipFree(p->d_table);
   if (p->d_err) (void)hipFree(p->d_err);
   if (p->d_ws) (void)hipFree(p->d_ws);
@@ -334,14 +307,13 @@ extern "C" int32_t fedavg_route_create(fedavg_route** out, int32_t device) {
   if (out == nullptr) return invalid("null out");
   *out = nullptr;
   if (device < 0) return invalid("bad device");
-  RT_HIP_TRY(hipSetDevice(device));
+  FEDAVG_TRY_HIP(hipSetDevice(device));
   fedavg_route* p = new fedavg_route();
   p->device = device;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_err), 3 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(p->d_err, 0, 3 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipDeviceSynchronize();  // the words are clear before any stream's first call
-  for (auto& sl : p->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
+  if (e == hipSuccess) e = p->ring.create();
   if (e != hipSuccess) {
     fedavg_route_destroy(p);
     return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("route state: ") + hipGetErrorString(e)).c_str());
@@ -403,7 +375,7 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
   if (C > 0x7fffffffll) return invalid("too many want lists");
   chunk_off[N] = static_cast<int32_t>(C);
 
-  RT_HIP_TRY(hipSetDevice(p->device));
+  FEDAVG_TRY_HIP(hipSetDevice(p->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
 
   // the table: grown on demand, empty (-1) between calls
@@ -412,17 +384,17 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
     if (cap < 4096) cap = 4096;
     if (cap > kRtMaxNodeSpace) cap = kRtMaxNodeSpace;
     if (p->d_table) {
-      RT_HIP_TRY(hipStreamSynchronize(s));
-      RT_HIP_TRY(hipFree(p->d_table));
+      FEDAVG_TRY_HIP(hipStreamSynchronize(s));
+      FEDAVG_TRY_HIP(hipFree(p->d_table));
       p->d_table = nullptr;
       p->table_cap = 0;
     }
-    RT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_table), sizeof(int32_t) * static_cast<size_t>(cap)));
+    FEDAVG_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_table), sizeof(int32_t) * static_cast<size_t>(cap)));
     p->table_cap = cap;
     p->dirty = true;
   }
   if (p->dirty && p->d_table != nullptr) {
-    RT_HIP_TRY(hipMemsetAsync(p->d_table, 0xff, sizeof(int32_t) * static_cast<size_t>(p->table_cap), s));
+    FEDAVG_TRY_HIP(hipMemsetAsync(p->d_table, 0xff, sizeof(int32_t) * static_cast<size_t>(p->table_cap), s));
     p->dirty = false;
   }
 
@@ -430,13 +402,13 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
   const size_t ws_bytes = sizeof(int32_t) * (static_cast<size_t>(B) + 2 * static_cast<size_t>(C));
   if (p->ws_cap < ws_bytes) {
     if (p->d_ws) {
-      RT_HIP_TRY(hipStreamSynchronize(s));
-      RT_HIP_TRY(hipFree(p->d_ws));
+      FEDAVG_TRY_HIP(hipStreamSynchronize(s));
+      FEDAVG_TRY_HIP(hipFree(p->d_ws));
       p->d_ws = nullptr;
       p->ws_cap = 0;
     }
     const size_t cap = ws_bytes * 2 < 64 * 1024 ? 64 * 1024 : ws_bytes * 2;
-    RT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_ws), cap));
+    FEDAVG_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_ws), cap));
     p->ws_cap = cap;
   }
 
@@ -448,19 +420,9 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
   const size_t list_bytes = sizeof(int32_t) * (static_cast<size_t>(N) + 1);
   const size_t o_chunks = ptr_bytes, o_roff = o_chunks + chunk_bytes, o_woff = o_roff + roff_bytes,
                o_coff = o_woff + list_bytes, bytes = o_coff + list_bytes;
-  fedavg_route::Slot& sl = p->slots[p->next];
-  if (sl.used) RT_HIP_TRY(hipEventSynchronize(sl.done));  // the launches that read this slot's tables
-  sl.used = false;
-  if (sl.cap < bytes) {
-    if (sl.host) RT_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) RT_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    RT_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    RT_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(p->ring.peek(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   if (S > 0) std::memcpy(sl.host, src_ptrs, ptr_bytes);
   RChunk* const h_chunks = reinterpret_cast<RChunk*>(sl.host + o_chunks);
   int32_t* const h_roff = reinterpret_cast<int32_t*>(sl.host + o_roff);
@@ -474,7 +436,7 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
     for (int32_t st = 0; st < len; st += kRtChunk) *q++ = RChunk{j, st};
   }
   std::memcpy(sl.host + o_coff, chunk_off.data(), list_bytes);
-  RT_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(p->ring.submit(sl, bytes, s));
 
   RArgs a;
   a.table = p->d_table;
@@ -528,21 +490,14 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
     int64_t split = (static_cast<int64_t>(kRtChunk) * row_bytes + kRtSplitBytes - 1) / kRtSplitBytes;
     split = split < 1 ? 1 : split > kRtMaxSplit ? kRtMaxSplit : split;
     const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(split));
-    if (vec) hipLaunchKernelGGL(route_gather_kernel<rt_u32x4>, grid, block, 0, s, a);
+    if (vec) hipLaunchKernelGGL(route_gather_kernel<u32x4>, grid, block, 0, s, a);
     else if (elem_bytes == 8) hipLaunchKernelGGL(route_gather_kernel<uint64_t>, grid, block, 0, s, a);
     else if (elem_bytes == 4) hipLaunchKernelGGL(route_gather_kernel<uint32_t>, grid, block, 0, s, a);
     else if (elem_bytes == 2) hipLaunchKernelGGL(route_gather_kernel<uint16_t>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(route_gather_kernel<uint8_t>, grid, block, 0, s, a);
     e = hipGetLastError();
   }
-  // the copy is on the stream whatever became of the launches: the slot is guarded either way
-  const hipError_t er = hipEventRecord(sl.done, s);
-  if (er == hipSuccess) {
-    sl.used = true;
-    p->next ^= 1;
-  } else {
-    (void)hipStreamSynchronize(s);  // no event to wait for: leave the slot idle before it is reused
-  }
+  const hipError_t er = p->ring.commit(sl, s);
   if (e == hipSuccess) e = er;
   if (e != hipSuccess)
     return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("route launch: ") + hipGetErrorString(e)).c_str());
@@ -552,14 +507,14 @@ extern "C" int32_t fedavg_route_rows(fedavg_route* p, const void* const* src_ptr
 extern "C" int32_t fedavg_route_errors(fedavg_route* p, void* stream, int32_t* out) {
   if (p == nullptr || out == nullptr) return invalid("null route handle or out");
   *out = 0;
-  RT_HIP_TRY(hipSetDevice(p->device));
+  FEDAVG_TRY_HIP(hipSetDevice(p->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  RT_HIP_TRY(hipStreamSynchronize(s));
+  FEDAVG_TRY_HIP(hipStreamSynchronize(s));
   uint32_t words[3] = {0, 0, 0};
-  RT_HIP_TRY(hipMemcpy(words, p->d_err, sizeof(words), hipMemcpyDeviceToHost));
+  FEDAVG_TRY_HIP(hipMemcpy(words, p->d_err, sizeof(words), hipMemcpyDeviceToHost));
   if ((words[0] | words[1] | words[2]) != 0) {  // reported once: the handle stays usable
-    RT_HIP_TRY(hipMemsetAsync(p->d_err, 0, sizeof(words), s));
-    RT_HIP_TRY(hipStreamSynchronize(s));
+    FEDAVG_TRY_HIP(hipMemsetAsync(p->d_err, 0, sizeof(words), s));
+    FEDAVG_TRY_HIP(hipStreamSynchronize(s));
   }
   *out = (words[0] ? 1 : 0) | (words[1] ? 2 : 0) | (words[2] ? 4 : 0);
   return FEDAVG_OK;

@@ -41,7 +41,8 @@
 #include <string>
 #include <vector>
 
-#include "sparse_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -53,14 +54,9 @@ constexpr int kSpMaxClients = FEDAVG_POINT_MAX_CLIENTS;
 constexpr int kSpCheckSlices = 4;  // workgroups per (client, tensor) index array in the check
 static_assert(kSpPerLane * kSpThreads == kSpTile && kSpTile <= 65535, "tile geometry");
 
-struct STile {
-  int32_t seg;
-  int32_t count;  // elements in this tile (kSpTile except at a segment's end)
-  int64_t start;  // first element, relative to the segment
-};
 
 struct SArgs {
-  const STile* tiles;
+  const Span* tiles;
   const int32_t* const* idx;   // [n][num_segments]; NULL only where nnz == 0
   const void* const* val;      // [n][num_segments]
   const int32_t* nnz;          // [n][num_segments], 0 <= nnz <= numel
@@ -75,48 +71,37 @@ struct SArgs {
   int32_t n;
 };
 
-struct bf16_t {
-  uint16_t bits;
-};
-
-#define SP_AS_GLOBAL __attribute__((address_space(1)))
-#define SP_AS_CONST __attribute__((address_space(4)))
-
 // entry j of a client's value array -> fp64, exactly
 template <typename V>
 __device__ __forceinline__ double sp_value(const void* p, int j);
 template <>
 __device__ __forceinline__ double sp_value<float>(const void* p, int j) {
-  return static_cast<double>(((const float SP_AS_GLOBAL*)p)[j]);
+  return static_cast<double>(((const float FEDAVG_AS_GLOBAL*)p)[j]);
 }
 template <>
 __device__ __forceinline__ double sp_value<__half>(const void* p, int j) {
-  const uint16_t h = ((const uint16_t SP_AS_GLOBAL*)p)[j];
+  const uint16_t h = ((const uint16_t FEDAVG_AS_GLOBAL*)p)[j];
   return static_cast<double>(__half2float(__ushort_as_half(static_cast<unsigned short>(h))));
 }
 template <>
 __device__ __forceinline__ double sp_value<bf16_t>(const void* p, int j) {
-  const uint32_t h = ((const uint16_t SP_AS_GLOBAL*)p)[j];
+  const uint32_t h = ((const uint16_t FEDAVG_AS_GLOBAL*)p)[j];
   return static_cast<double>(__uint_as_float(h << 16));
 }
 template <>
 __device__ __forceinline__ double sp_value<double>(const void* p, int j) {
-  return ((const double SP_AS_GLOBAL*)p)[j];
+  return ((const double FEDAVG_AS_GLOBAL*)p)[j];
 }
 
 // first position in [lo, hi) whose index is >= key (hi if none); reads inside [lo, hi) only
 __device__ __forceinline__ int sp_lower_bound(const int32_t* p, int lo, int hi, int64_t key) {
-  const int32_t SP_AS_GLOBAL* q = (const int32_t SP_AS_GLOBAL*)p;
+  const int32_t FEDAVG_AS_GLOBAL* q = (const int32_t FEDAVG_AS_GLOBAL*)p;
   while (lo < hi) {
     const int mid = lo + ((hi - lo) >> 1);
     if (static_cast<int64_t>(q[mid]) < key) lo = mid + 1;
     else hi = mid;
   }
   return lo;
-}
-
-__device__ __forceinline__ void sp_raise(uint32_t* word) {
-  __hip_atomic_store(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -132,7 +117,7 @@ __global__ __launch_bounds__(kSpThreads) void sparse_fold_kernel(SArgs a) {
 
   const int t = static_cast<int>(threadIdx.x);
   const int lane = t & 63;
-  const STile SP_AS_CONST* tp = (const STile SP_AS_CONST*)(a.tiles + blockIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
   const int32_t seg = tp->seg;
   const int32_t count = tp->count;
   const int64_t start = tp->start;
@@ -159,7 +144,7 @@ __global__ __launch_bounds__(kSpThreads) void sparse_fold_kernel(SArgs a) {
   // the lane's base values, kept for the whole tile (+0.0 past the tile's end)
   double b[K];
   {
-    const double SP_AS_GLOBAL* pb = (const double SP_AS_GLOBAL*)a.base[seg] + start;
+    const double FEDAVG_AS_GLOBAL* pb = (const double FEDAVG_AS_GLOBAL*)a.base[seg] + start;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int e = k * kSpThreads + t;
@@ -206,7 +191,7 @@ __global__ __launch_bounds__(kSpThreads) void sparse_fold_kernel(SArgs a) {
         }
       }
       const int j = l + (f - o);
-      const int64_t rel = static_cast<int64_t>(((const int32_t SP_AS_GLOBAL*)ipq)[j]) - start;
+      const int64_t rel = static_cast<int64_t>(((const int32_t FEDAVG_AS_GLOBAL*)ipq)[j]) - start;
       // into the plane only when the index lies inside this tile; otherwise the entry is dropped
       if (rel >= 0 && rel < count) plane[q * kSpTile + static_cast<int>(rel)] = sp_value<V>(vpq, j);
     }
@@ -235,7 +220,7 @@ __global__ __launch_bounds__(kSpThreads) void sparse_fold_kernel(SArgs a) {
 
   // out = acc / W
   bool nan_acc = false, nan_out = false;
-  O SP_AS_GLOBAL* po = (O SP_AS_GLOBAL*)a.outs[seg] + start;
+  O FEDAVG_AS_GLOBAL* po = (O FEDAVG_AS_GLOBAL*)a.outs[seg] + start;
   const double divisor = a.divisor;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -248,9 +233,9 @@ __global__ __launch_bounds__(kSpThreads) void sparse_fold_kernel(SArgs a) {
       po[e] = static_cast<O>(r);
     }
   }
-  if (__ballot(nan_in) != 0ull && lane == 0) sp_raise(a.flag + 2);
-  if (__ballot(nan_acc) != 0ull && lane == 0) sp_raise(a.flag + 0);
-  if (__ballot(nan_out) != 0ull && lane == 0) sp_raise(a.flag + 1);
+  if (__ballot(nan_in) != 0ull && lane == 0) raise_flag(a.flag, 2);
+  if (__ballot(nan_acc) != 0ull && lane == 0) raise_flag(a.flag, 0);
+  if (__ballot(nan_out) != 0ull && lane == 0) raise_flag(a.flag, 1);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -260,7 +245,7 @@ __global__ __launch_bounds__(kSpThreads) void sparse_check_kernel(SArgs a) {
   const int64_t pair = blockIdx.x;
   const int nz = a.nnz[pair];
   if (nz <= 0) return;
-  const int32_t SP_AS_GLOBAL* ip = (const int32_t SP_AS_GLOBAL*)a.idx[pair];
+  const int32_t FEDAVG_AS_GLOBAL* ip = (const int32_t FEDAVG_AS_GLOBAL*)a.idx[pair];
   const int32_t numel = a.numel[pair % a.num_segments];
   const int t = static_cast<int>(threadIdx.x);
   bool bad = false;
@@ -269,81 +254,50 @@ __global__ __launch_bounds__(kSpThreads) void sparse_check_kernel(SArgs a) {
     const int32_t i = ip[j];
     bad |= i < 0 || i >= numel || (j > 0 && i <= ip[j - 1]);
   }
-  if (__ballot(bad) != 0ull && (t & 63) == 0) sp_raise(a.bad);
+  if (__ballot(bad) != 0ull && (t & 63) == 0) raise_flag(a.bad, 0);
 }
 
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 struct SparseState {
-  STile* d_tiles = nullptr;
+  Span* d_tiles = nullptr;
   int64_t num_tiles = 0;
   int32_t* d_numel = nullptr;  // [num_segments]
   uint32_t* d_bad = nullptr;   // latched by sparse_check_kernel, cleared by fedavg_sparse_index_errors
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's tables
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launches that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;
+  ~SparseState() {
+    ring.release();
+    if (d_tiles) (void)hipFree(d_tiles);
+    if (d_numel) (void)hipFree(d_numel);
+    if (d_bad) (void)hipFree(d_bad);
+  }
 };
 
-#define SP_HIP_TRY(expr)                                                                              \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
-void free_state(SparseState* st) {
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  if (st->d_tiles) (void)hipFree(st->d_tiles);
-  if (st->d_numel) (void)hipFree(st->d_numel);
-  if (st->d_bad) (void)hipFree(st->d_bad);
-  delete st;
-}
-
 int32_t ensure_state(const fedavg_robust_view& v, void** slot, SparseState** out) {
-  if (*slot != nullptr) {
-    *out = static_cast<SparseState*>(*slot);
-    return FEDAVG_OK;
-  }
-  std::vector<STile> tiles;
-  std::vector<int32_t> numel(static_cast<size_t>(v.num_segments));
-  for (int32_t t = 0; t < v.num_segments; ++t) {
-    numel[t] = static_cast<int32_t>(v.seg_numel[t]);  // <= INT32_MAX: checked by the caller
-    for (int64_t s = 0; s < v.seg_numel[t]; s += kSpTile) {
-      const int64_t left = v.seg_numel[t] - s;
-      tiles.push_back(STile{t, static_cast<int32_t>(left < kSpTile ? left : kSpTile), s});
+  if (*slot == nullptr) {
+    std::vector<int32_t> numel(static_cast<size_t>(v.num_segments));
+    for (int32_t t = 0; t < v.num_segments; ++t)
+      numel[t] = static_cast<int32_t>(v.seg_numel[t]);  // <= INT32_MAX: checked by the caller
+    SparseState* st = new SparseState();
+    int32_t r = span_table(v.seg_numel, v.num_segments, kSpTile, "sparse fold", "sparse tile table", &st->d_tiles,
+                           &st->num_tiles);
+    if (r == FEDAVG_OK) {
+      hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_numel), sizeof(int32_t) * numel.size());
+      if (e == hipSuccess) e = hipMemcpy(st->d_numel, numel.data(), sizeof(int32_t) * numel.size(), hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&st->d_bad), sizeof(uint32_t));
+      if (e == hipSuccess) e = hipMemset(st->d_bad, 0, sizeof(uint32_t));
+      if (e == hipSuccess) e = hipDeviceSynchronize();  // the word is clear before any stream's first check
+      if (e == hipSuccess) e = st->ring.create();
+      r = hip_status("sparse tile table", e);
     }
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
+    }
+    *slot = st;
   }
-  if (tiles.empty() || tiles.size() > 0x7fffffffull) return invalid("layout too large for one sparse fold");
-  SparseState* st = new SparseState();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_tiles), sizeof(STile) * tiles.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_tiles, tiles.data(), sizeof(STile) * tiles.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&st->d_numel), sizeof(int32_t) * numel.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_numel, numel.data(), sizeof(int32_t) * numel.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&st->d_bad), sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemset(st->d_bad, 0, sizeof(uint32_t));
-  if (e == hipSuccess) e = hipDeviceSynchronize();  // the word is clear before any stream's first check
-  for (auto& sl : st->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    free_state(st);
-    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("sparse tile table: ") + hipGetErrorString(e)).c_str());
-  }
-  st->num_tiles = static_cast<int64_t>(tiles.size());
-  *slot = st;
-  *out = st;
+  *out = static_cast<SparseState*>(*slot);
   return FEDAVG_OK;
 }
 
@@ -370,10 +324,9 @@ int32_t fedavg_internal_sparse_constant(const char* name, int64_t* out) {
 }
 
 void fedavg_internal_sparse_release(int32_t device, void* state) {
-  SparseState* st = static_cast<SparseState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  free_state(st);
+  delete static_cast<SparseState*>(state);
 }
 
 extern "C" int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx, const int32_t* const* index_ptrs,
@@ -385,7 +338,7 @@ extern "C" int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx, const int32_t*
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_sparse_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_SPARSE, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (value_dtype != FEDAVG_F32 && value_dtype != FEDAVG_F16 && value_dtype != FEDAVG_BF16 && value_dtype != FEDAVG_F64)
@@ -435,7 +388,7 @@ extern "C" int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx, const int32_t*
       return invalid("segment " + std::to_string(t) + ": the fold is not in-place (out == base)");
   }
 
-  SP_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   SparseState* st = nullptr;
   const int32_t re = ensure_state(v, slot, &st);
   if (re != FEDAVG_OK) return re;
@@ -450,19 +403,9 @@ extern "C" int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx, const int32_t*
   const size_t bytes = 2 * ptr_bytes + 2 * seg_bytes + w_bytes + nnz_bytes;
   // `next` advances only once work that reads this slot has been enqueued and its event recorded: a
   // call that fails before that leaves the slot idle and is simply followed by a call on the same slot
-  SparseState::Slot& sl = st->slots[st->next];
-  if (sl.used) SP_HIP_TRY(hipEventSynchronize(sl.done));  // the launches that read this slot's tables
-  sl.used = false;
-  if (sl.cap < bytes) {
-    if (sl.host) SP_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) SP_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    SP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    SP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.peek(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   const size_t o_val = ptr_bytes, o_base = 2 * ptr_bytes, o_out = o_base + seg_bytes, o_w = o_out + seg_bytes,
                o_nnz = o_w + w_bytes;
   std::memcpy(sl.host, index_ptrs, ptr_bytes);
@@ -472,7 +415,7 @@ extern "C" int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx, const int32_t*
   std::memcpy(sl.host + o_w, weights, w_bytes);
   int32_t* const h_nnz = reinterpret_cast<int32_t*>(sl.host + o_nnz);
   for (size_t i = 0; i < entries; ++i) h_nnz[i] = static_cast<int32_t>(nnz[i]);
-  SP_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
 
   SArgs a;
   a.tiles = st->d_tiles;
@@ -497,14 +440,7 @@ extern "C" int32_t fedavg_sparse_aggregate_delta(fedavg_ctx* ctx, const int32_t*
     else launch<double>(value_dtype, grid, block, s, a);
     e = hipGetLastError();
   }
-  // the copy is on the stream whatever became of the launches: the slot is guarded either way
-  const hipError_t er = hipEventRecord(sl.done, s);
-  if (er == hipSuccess) {
-    sl.used = true;
-    st->next ^= 1;
-  } else {
-    (void)hipStreamSynchronize(s);  // no event to wait for: leave the slot idle before it is reused
-  }
+  const hipError_t er = st->ring.commit(sl, s);
   if (e == hipSuccess) e = er;
   if (e != hipSuccess)
     return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("sparse fold launch: ") + hipGetErrorString(e)).c_str());
@@ -516,20 +452,20 @@ extern "C" int32_t fedavg_sparse_index_errors(fedavg_ctx* ctx, void* stream, int
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_sparse_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_SPARSE, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (out == nullptr) return invalid("null out");
   *out = 0;
   SparseState* st = static_cast<SparseState*>(*slot);
   if (st == nullptr) return FEDAVG_OK;  // no sparse fold has run on this context
-  SP_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  SP_HIP_TRY(hipStreamSynchronize(s));
+  FEDAVG_TRY_HIP(hipStreamSynchronize(s));
   uint32_t word = 0;
-  SP_HIP_TRY(hipMemcpy(&word, st->d_bad, sizeof(word), hipMemcpyDeviceToHost));
+  FEDAVG_TRY_HIP(hipMemcpy(&word, st->d_bad, sizeof(word), hipMemcpyDeviceToHost));
   if (word != 0) {  // reported once: the context stays usable (cleared on the stream, before its next launch)
-    SP_HIP_TRY(hipMemsetAsync(st->d_bad, 0, sizeof(word), s));
-    SP_HIP_TRY(hipStreamSynchronize(s));
+    FEDAVG_TRY_HIP(hipMemsetAsync(st->d_bad, 0, sizeof(word), s));
+    FEDAVG_TRY_HIP(hipStreamSynchronize(s));
   }
   *out = word != 0 ? 1 : 0;
   return FEDAVG_OK;

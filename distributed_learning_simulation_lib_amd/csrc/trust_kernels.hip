@@ -41,7 +41,8 @@
 #include <string>
 #include <vector>
 
-#include "trust_internal.h"
+#include "call_tables.h"
+#include "device_common.h"
 
 namespace {
 
@@ -56,14 +57,9 @@ static_assert(kTrustThreads % 64 == 0 && 2 * kTrustBatch <= kTrustThreads, "geom
 static_assert(kTrustRedCols * (kTrustThreads / kTrustRedCols) == kTrustThreads &&
               kTrustRedTile % (kTrustThreads / kTrustRedCols) == 0, "reduce geometry");
 
-struct TChunk {
-  int32_t seg;
-  int32_t count;  // elements in this chunk (kTrustChunk except at a segment's end)
-  int64_t start;  // first element, relative to the segment
-};
 
 struct TArgs {
-  const TChunk* chunks;
+  const Span* chunks;
   const void* const* ptrs;         // [n][num_segments], every entry non-NULL
   const double* const* centre;     // [num_segments], or NULL: the origin
   const double* const* direction;  // [num_segments]
@@ -73,109 +69,12 @@ struct TArgs {
   int32_t n;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-struct bf16_t {
-  uint16_t bits;
-};
-
-#define TRUST_AS_GLOBAL __attribute__((address_space(1)))
-#define TRUST_AS_CONST __attribute__((address_space(4)))
-
-// A client's 16 staged bytes -> fp64 values, exactly.
-template <typename T>
-struct TFormat;
-template <>
-struct TFormat<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float(raw[i]));
-  }
-};
-template <>
-struct TFormat<__half> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint32_t h = (raw[i / 2] >> (16 * (i % 2))) & 0xffffu;
-    return static_cast<double>(__half2float(__ushort_as_half(static_cast<unsigned short>(h))));
-  }
-};
-template <>
-struct TFormat<bf16_t> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    return static_cast<double>(__uint_as_float((raw[i / 2] >> (16 * (i % 2))) << 16));
-  }
-};
-template <>
-struct TFormat<double> {
-  static constexpr int N = 2;
-  __device__ __forceinline__ static double value(const u32x4& raw, int i) {
-    const uint64_t lo = raw[2 * i], hi = raw[2 * i + 1];
-    return __longlong_as_double(static_cast<long long>(lo | (hi << 32)));
-  }
-};
-
-// The 16 bytes element by element: only elements below `have` are read (a chunk's last vector at
-// a segment's end, or client storage that is not 16-byte aligned); the rest stay +0.0.
-template <typename T>
-__device__ __forceinline__ u32x4 trust_load_guarded(const void* base, int64_t elem, int have) {
-  constexpr int N = TFormat<T>::N;
-  u32x4 raw = {0u, 0u, 0u, 0u};
-  if constexpr (sizeof(T) == 2) {
-    const uint16_t TRUST_AS_GLOBAL* p = (const uint16_t TRUST_AS_GLOBAL*)base + elem;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) raw[i / 2] |= static_cast<uint32_t>(p[i]) << (16 * (i % 2));
-    }
-  } else {
-    constexpr int W = sizeof(T) / 4;  // 32-bit words per element
-    const uint32_t TRUST_AS_GLOBAL* p = (const uint32_t TRUST_AS_GLOBAL*)base + elem * W;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) raw[i * W + w] = p[i * W + w];
-      }
-    }
-  }
-  return raw;
-}
-
-// N fp64 values of a centre or direction segment from element `elem`: only elements below `have`
-// are read, the rest stay +0.0; 16-byte loads where the segment is 16-byte aligned.
-template <int N>
-__device__ __forceinline__ void trust_load_f64(double (&dst)[N], const double* base, int64_t elem, int have,
-                                               bool vec) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) dst[i] = 0.0;
-  if (base == nullptr || have <= 0) return;
-  const double TRUST_AS_GLOBAL* q = (const double TRUST_AS_GLOBAL*)base + elem;
-  if (have >= N && vec) {  // elem is even: 16-byte aligned with the segment
-#pragma unroll
-    for (int i = 0; i < N; i += 2) {
-      const f64x2 v = *(const f64x2 TRUST_AS_GLOBAL*)(q + i);
-      dst[i] = v[0];
-      dst[i + 1] = v[1];
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      if (i < have) dst[i] = q[i];
-    }
-  }
-}
-
-__device__ __forceinline__ void trust_raise_flag(uint32_t* flag, int word) {
-  __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // ---------------------------------------------------------------------------------------
 // the chunk kernel: blockIdx.x = chunk
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kTrustThreads) void trust_chunk_kernel(TArgs a) {
-  using F = TFormat<T>;
+  using F = Format<T>;
   constexpr int N = F::N;
   constexpr int K = kTrustChunk / (N * kTrustThreads);  // 16-byte vectors per lane and client
   static_assert(K >= 1 && K * N * kTrustThreads == kTrustChunk && N % 2 == 0, "chunk geometry");
@@ -185,7 +84,7 @@ __global__ __launch_bounds__(kTrustThreads) void trust_chunk_kernel(TArgs a) {
 
   const int t = static_cast<int>(threadIdx.x);
   const int lane = t & 63, wave = t >> 6;
-  const TChunk TRUST_AS_CONST* cp = (const TChunk TRUST_AS_CONST*)(a.chunks + blockIdx.x);
+  const Span FEDAVG_AS_CONST* cp = (const Span FEDAVG_AS_CONST*)(a.chunks + blockIdx.x);
   const int32_t seg = cp->seg;
   const int32_t count = cp->count;
   const int64_t start = cp->start;
@@ -206,8 +105,8 @@ __global__ __launch_bounds__(kTrustThreads) void trust_chunk_kernel(TArgs a) {
   for (int k = 0; k < K; ++k) {
     const int e0 = (k * kTrustThreads + t) * N;  // chunk-relative
     const int have = count - e0;
-    trust_load_f64<N>(v[k], pv, start + e0, have, pv_vec);
-    trust_load_f64<N>(g[k], pg, start + e0, have, pg_vec);
+    load_f64<N>(v[k], pv, start + e0, have, pv_vec);
+    load_f64<N>(g[k], pg, start + e0, have, pg_vec);
 #pragma unroll
     for (int i = 0; i < N; ++i) nan_in |= (v[k][i] != v[k][i]) | (g[k][i] != g[k][i]);
   }
@@ -223,10 +122,10 @@ __global__ __launch_bounds__(kTrustThreads) void trust_chunk_kernel(TArgs a) {
       u32x4 r = {0u, 0u, 0u, 0u};
       if (have > 0) {
         if (have >= N && vec) {
-          const u32x4 TRUST_AS_GLOBAL* q = (const u32x4 TRUST_AS_GLOBAL*)((const T TRUST_AS_GLOBAL*)p + (start + e0));
+          const u32x4 FEDAVG_AS_GLOBAL* q = (const u32x4 FEDAVG_AS_GLOBAL*)((const T FEDAVG_AS_GLOBAL*)p + (start + e0));
           r = __builtin_nontemporal_load(q);
         } else {
-          r = trust_load_guarded<T>(p, start + e0, have);
+          r = load_guarded<T>(p, start + e0, have);
         }
       }
       dst[k] = r;
@@ -284,7 +183,7 @@ __global__ __launch_bounds__(kTrustThreads) void trust_chunk_kernel(TArgs a) {
       reduce(bufb, c + 1);
     }
   }
-  if (__ballot(nan_in) != 0ull && lane == 0) trust_raise_flag(a.flag, 2);
+  if (__ballot(nan_in) != 0ull && lane == 0) raise_flag(a.flag, 2);
 }
 
 // A workgroup owns kTrustRedCols of the 2n columns: it stages kTrustRedTile chunk partials of each
@@ -325,7 +224,7 @@ __global__ __launch_bounds__(kTrustThreads) void trust_reduce_kernel(const doubl
   const int mine = static_cast<int>(blockIdx.x) * kTrustRedCols + t;
   if (t < kTrustRedCols && mine < cols) {
     out[mine] = s;
-    if (s != s) trust_raise_flag(flag, 0);  // inf - inf, 0 * inf, +inf + -inf (or a NaN input, flagged at the load too)
+    if (s != s) raise_flag(flag, 0);  // inf - inf, 0 * inf, +inf + -inf (or a NaN input, flagged at the load too)
   }
 }
 
@@ -333,57 +232,31 @@ __global__ __launch_bounds__(kTrustThreads) void trust_reduce_kernel(const doubl
 // host side
 // ---------------------------------------------------------------------------------------
 struct TrustState {
-  TChunk* d_chunks = nullptr;
+  Span* d_chunks = nullptr;
   int64_t num_chunks = 0;
   double* ws = nullptr;  // grown lazily to the largest client count seen
   size_t ws_bytes = 0;
-  struct Slot {
-    char* host = nullptr;  // pinned image of a call's pointer tables (clients, direction, centre)
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // the launch that read `dev` finished
-    bool used = false;
-  } slots[2];
-  int next = 0;
+  TableRing ring;  // a call's tables: clients, direction, centre
+  ~TrustState() {
+    ring.release();
+    if (d_chunks) (void)hipFree(d_chunks);
+    if (ws) (void)hipFree(ws);
+  }
 };
 
-#define TRUST_HIP_TRY(expr)                                                                           \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t invalid(const std::string& msg) { return fedavg_internal_fail(FEDAVG_ERR_INVALID, msg.c_str()); }
-
 int32_t ensure_state(const fedavg_robust_view& v, void** slot, TrustState** out) {
-  if (*slot != nullptr) {
-    *out = static_cast<TrustState*>(*slot);
-    return FEDAVG_OK;
-  }
-  std::vector<TChunk> chunks;
-  for (int32_t t = 0; t < v.num_segments; ++t) {
-    for (int64_t s = 0; s < v.seg_numel[t]; s += kTrustChunk) {
-      const int64_t left = v.seg_numel[t] - s;
-      chunks.push_back(TChunk{t, static_cast<int32_t>(left < kTrustChunk ? left : kTrustChunk), s});
+  if (*slot == nullptr) {
+    TrustState* st = new TrustState();
+    int32_t r = span_table(v.seg_numel, v.num_segments, kTrustChunk, "moments launch", "trust chunk table", &st->d_chunks,
+                           &st->num_chunks);
+    if (r == FEDAVG_OK) r = hip_status("trust chunk table", st->ring.create());
+    if (r != FEDAVG_OK) {
+      delete st;
+      return r;
     }
+    *slot = st;
   }
-  if (chunks.empty() || chunks.size() > 0x7fffffffull) return invalid("layout too large for one moments launch");
-  TrustState* st = new TrustState();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_chunks), sizeof(TChunk) * chunks.size());
-  if (e == hipSuccess) e = hipMemcpy(st->d_chunks, chunks.data(), sizeof(TChunk) * chunks.size(), hipMemcpyHostToDevice);
-  for (auto& sl : st->slots)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    if (st->d_chunks) (void)hipFree(st->d_chunks);
-    for (auto& sl : st->slots)
-      if (sl.done) (void)hipEventDestroy(sl.done);
-    delete st;
-    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("trust chunk table: ") + hipGetErrorString(e)).c_str());
-  }
-  st->num_chunks = static_cast<int64_t>(chunks.size());
-  *slot = st;
-  *out = st;
+  *out = static_cast<TrustState*>(*slot);
   return FEDAVG_OK;
 }
 
@@ -395,27 +268,18 @@ int32_t fedavg_internal_trust_constant(const char* name, int64_t* out) {
   else if (n == "trust_threads") *out = kTrustThreads;
   else if (n == "trust_batch") *out = kTrustBatch;
   else if (n == "trust_max_clients") *out = kTrustMaxClients;
-  else if (n == "trust_ae_f32") *out = TFormat<float>::N;
-  else if (n == "trust_ae_f16") *out = TFormat<__half>::N;
-  else if (n == "trust_ae_bf16") *out = TFormat<bf16_t>::N;
-  else if (n == "trust_ae_f64") *out = TFormat<double>::N;
+  else if (n == "trust_ae_f32") *out = Format<float>::N;
+  else if (n == "trust_ae_f16") *out = Format<__half>::N;
+  else if (n == "trust_ae_bf16") *out = Format<bf16_t>::N;
+  else if (n == "trust_ae_f64") *out = Format<double>::N;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
 
 void fedavg_internal_trust_release(int32_t device, void* state) {
-  TrustState* st = static_cast<TrustState*>(state);
-  if (st == nullptr) return;
+  if (state == nullptr) return;
   (void)hipSetDevice(device);
-  for (auto& sl : st->slots) {
-    if (sl.used) (void)hipEventSynchronize(sl.done);
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  if (st->d_chunks) (void)hipFree(st->d_chunks);
-  if (st->ws) (void)hipFree(st->ws);
-  delete st;
+  delete static_cast<TrustState*>(state);
 }
 
 extern "C" int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
@@ -425,7 +289,7 @@ extern "C" int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const
   const int32_t rv = fedavg_internal_robust_view(ctx, &v);
   if (rv != FEDAVG_OK) return rv;
   void** slot = nullptr;
-  const int32_t rs = fedavg_internal_trust_slot(ctx, &slot);
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_TRUST, &slot);
   if (rs != FEDAVG_OK) return rs;
   if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
   if (in_dtype != FEDAVG_F32 && in_dtype != FEDAVG_F16 && in_dtype != FEDAVG_BF16 && in_dtype != FEDAVG_F64)
@@ -458,7 +322,7 @@ extern "C" int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const
     }
   }
 
-  TRUST_HIP_TRY(hipSetDevice(v.device));
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
   TrustState* st = nullptr;
   const int32_t re = ensure_state(v, slot, &st);
   if (re != FEDAVG_OK) return re;
@@ -467,10 +331,10 @@ extern "C" int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const
   const size_t ws_bytes =
       sizeof(double) * static_cast<size_t>(st->num_chunks) * 2 * static_cast<size_t>(num_clients);
   if (st->ws_bytes < ws_bytes) {
-    if (st->ws) TRUST_HIP_TRY(hipFree(st->ws));  // synchronises with the launches that used it
+    if (st->ws) FEDAVG_TRY_HIP(hipFree(st->ws));  // synchronises with the launches that used it
     st->ws = nullptr;
     st->ws_bytes = 0;
-    TRUST_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->ws), ws_bytes));
+    FEDAVG_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&st->ws), ws_bytes));
     st->ws_bytes = ws_bytes;
   }
 
@@ -478,23 +342,13 @@ extern "C" int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const
   const size_t client_bytes = sizeof(void*) * entries;
   const size_t seg_bytes = sizeof(void*) * static_cast<size_t>(T);
   const size_t bytes = client_bytes + seg_bytes + (centre_ptrs != nullptr ? seg_bytes : 0);
-  TrustState::Slot& sl = st->slots[st->next];
-  st->next ^= 1;
-  if (sl.used) TRUST_HIP_TRY(hipEventSynchronize(sl.done));  // the launch that read this slot's table
-  if (sl.cap < bytes) {
-    if (sl.host) TRUST_HIP_TRY(hipHostFree(sl.host));
-    if (sl.dev) TRUST_HIP_TRY(hipFree(sl.dev));
-    sl.host = sl.dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = bytes * 2 < 64 * 1024 ? 64 * 1024 : bytes * 2;
-    TRUST_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap, hipHostMallocDefault));
-    TRUST_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sl.dev), cap));
-    sl.cap = cap;
-  }
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.acquire(bytes, &slp));
+  TableRing::Slot& sl = *slp;
   std::memcpy(sl.host, client_ptrs, client_bytes);
   std::memcpy(sl.host + client_bytes, direction_ptrs, seg_bytes);
   if (centre_ptrs != nullptr) std::memcpy(sl.host + client_bytes + seg_bytes, centre_ptrs, seg_bytes);
-  TRUST_HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
 
   TArgs a;
   a.chunks = st->d_chunks;
@@ -513,13 +367,11 @@ extern "C" int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const
     case FEDAVG_BF16: hipLaunchKernelGGL(trust_chunk_kernel<bf16_t>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(trust_chunk_kernel<double>, grid, block, 0, s, a); break;
   }
-  TRUST_HIP_TRY(hipGetLastError());
+  FEDAVG_TRY_HIP(hipGetLastError());
   const int32_t cols = 2 * num_clients;
   const unsigned groups = (static_cast<unsigned>(cols) + kTrustRedCols - 1) / kTrustRedCols;
   hipLaunchKernelGGL(trust_reduce_kernel, dim3(groups), block, 0, s, st->ws, static_cast<int32_t>(st->num_chunks),
                      cols, out, v.d_flag);
-  TRUST_HIP_TRY(hipGetLastError());
-  TRUST_HIP_TRY(hipEventRecord(sl.done, s));
-  sl.used = true;
-  return FEDAVG_OK;
+  FEDAVG_TRY_HIP(hipGetLastError());
+  return st->ring.retire(sl, s);
 }
