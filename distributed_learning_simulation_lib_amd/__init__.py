@@ -26,6 +26,14 @@ from .algorithm import (
     SparseFedAVGAlgorithm,
 )
 from .algorithm_repository import AlgorithmRepository
+from .dp import (
+    DifferentialPrivacyEmbeddingEndpoint,
+    DifferentialPrivacyParameterEndpoint,
+    add_dp_noise,
+    add_dp_noise_to_parameter,
+    compute_dp_sigma,
+    normal_stream,
+)
 from .fedavg import ClientTable, FedAvgContext, ModelLayout, NaNAggregationError
 from .message import (
     DeltaParameterMessage,
@@ -49,6 +57,8 @@ __all__ = [
     "ClippedFedAVGAlgorithm",
     "CompositeAggregationAlgorithm",
     "DeltaParameterMessage",
+    "DifferentialPrivacyEmbeddingEndpoint",
+    "DifferentialPrivacyParameterEndpoint",
     "FeatureMessage",
     "FedAVGAlgorithm",
     "FLTrustFedAVGAlgorithm",
@@ -70,7 +80,11 @@ __all__ = [
     "ServerOptFedAVGAlgorithm",
     "SparseDelta",
     "SparseFedAVGAlgorithm",
+    "add_dp_noise",
+    "add_dp_noise_to_parameter",
+    "compute_dp_sigma",
     "get_message_size",
+    "normal_stream",
     "philox_uniforms",
     "topk_sparsify",
 ]
@@ -185,6 +199,18 @@ def _register_builtin() -> None:
             client_cls=None,  # type: ignore[arg-type]
             server_cls=AggregationServer,
             algorithm_cls=GraphAlgorithm,
+        )
+    # FedAvg whose workers clip and noise their updates before sending (the Gaussian mechanism): the
+    # plain server and rule behind the differential-privacy client endpoint
+    if not AlgorithmRepository.has_algorithm("fed_avg_dp"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_avg_dp",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            client_endpoint_cls=DifferentialPrivacyParameterEndpoint,
+            algorithm_cls=FedAVGAlgorithm,
         )
 
 

@@ -1,5 +1,5 @@
 // Device-side helpers the side modules (<module>_kernels.hip) share: the 16-byte vector types, the
-// staged-bytes-to-fp64 formats, the guarded loads and the NaN-flag store. Everything here is
+// staged-bytes-to-fp64 formats, the guarded loads, the NaN-flag store and the Philox block. Everything here is
 // inlined into the kernel that calls it; fedavg_kernels.hip and personalized_kernels.hip keep their own.
 #pragma once
 
@@ -106,4 +106,32 @@ __device__ __forceinline__ void load_f64(double (&dst)[N], const double* base, i
 // Latches word `word` of a flag block (the context's NaN words, a module's error words).
 __device__ __forceinline__ void raise_flag(uint32_t* flag, int word) {
   __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): the block of counter (c0, c1, c2, c3) under key
+// (k0, k1). The streams of the broadcast encoder and of the clip-and-noise pass are cut from it.
+struct QWords {
+  uint32_t w[4];
+};
+
+__device__ __forceinline__ QWords q_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                           uint32_t k1) {
+  constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
+    const uint32_t hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += kW0;
+    k1 += kW1;
+  }
+  QWords o;
+  o.w[0] = c0;
+  o.w[1] = c1;
+  o.w[2] = c2;
+  o.w[3] = c3;
+  return o;
 }

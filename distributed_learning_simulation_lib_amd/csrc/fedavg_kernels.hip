@@ -3006,6 +3006,7 @@ const SideModule kSideModules[FEDAVG_MODULES] = {
     {fedavg_internal_sparse_constant, fedavg_internal_sparse_release},
     {fedavg_internal_route_constant, nullptr},
     {fedavg_internal_quant_constant, fedavg_internal_quant_release},
+    {fedavg_internal_dp_constant, fedavg_internal_dp_release},
 };
 
 bool side_constant(const char* name, int64_t* v) {

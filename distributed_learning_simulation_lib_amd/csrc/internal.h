@@ -21,6 +21,7 @@ enum fedavg_module {
   FEDAVG_MODULE_SPARSE,
   FEDAVG_MODULE_ROUTE,
   FEDAVG_MODULE_QUANT,
+  FEDAVG_MODULE_DP,
   FEDAVG_MODULES
 };
 
@@ -50,6 +51,7 @@ FEDAVG_INTERNAL int32_t fedavg_internal_opt_constant(const char* name, int64_t* 
 FEDAVG_INTERNAL int32_t fedavg_internal_sparse_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL int32_t fedavg_internal_route_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL int32_t fedavg_internal_quant_constant(const char* name, int64_t* out);
+FEDAVG_INTERNAL int32_t fedavg_internal_dp_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL void fedavg_internal_robust_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_krum_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_point_release(int32_t device, void* state);
@@ -58,3 +60,4 @@ FEDAVG_INTERNAL void fedavg_internal_trust_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_opt_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_sparse_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_quant_release(int32_t device, void* state);
+FEDAVG_INTERNAL void fedavg_internal_dp_release(int32_t device, void* state);

@@ -208,35 +208,9 @@ __global__ __launch_bounds__(kQThreads) void quant_header_kernel(QArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
-// the uniform stream: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), key = the seed's two
-// halves, counter = (block low, block high, tensor id, draw)
+// the uniform stream: Philox4x32-10 (q_philox, device_common.h), key = the seed's two halves,
+// counter = (block low, block high, tensor id, draw)
 // ---------------------------------------------------------------------------------------
-struct QWords {
-  uint32_t w[4];
-};
-
-__device__ __forceinline__ QWords q_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                           uint32_t k1) {
-  constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
-    const uint32_t hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += kW0;
-    k1 += kW1;
-  }
-  QWords o;
-  o.w[0] = c0;
-  o.w[1] = c1;
-  o.w[2] = c2;
-  o.w[3] = c3;
-  return o;
-}
-
 // the uniforms of the aligned group of 4 (fp32) or 2 (fp64) elements that starts at element e
 template <typename F>
 struct QUniform;

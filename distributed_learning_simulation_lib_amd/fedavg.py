@@ -1203,6 +1203,47 @@ class FedAvgContext:
             )
         )
 
+    def dp_noise(self, tensors: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], C: float, noise_scale: float,
+                 seed: int = 0, draw: int = 0, tensor_ids: Sequence[int] | None = None, row_len: int = 0) -> None:
+        """Clip and noise ``tensors`` (contiguous tensors of one floating dtype on the context's
+        device, of any sizes: the context's layout plays no part) into ``outs`` in three launches
+        (``fedavg_dp_noise``). ``row_len == 0``: all tensors together are one vector
+        with one L2 norm; ``row_len > 0``: one tensor whose rows of ``row_len`` elements each have
+        their own. ``outs[t]`` has the dtype and size of ``tensors[t]`` and may be ``tensors[t]``
+        itself. ``noise_scale`` is ``sigma * C``; ``tensor_ids[t]`` is the tensor's word of the normal
+        stream's counter (default: its position). Asynchronous; a non-finite element latches the
+        input flag (``flags()``)."""
+        T = len(tensors)
+        if T == 0 or len(outs) != T:
+            raise ValueError("one output per tensor and at least one tensor are required")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
+            raise ValueError("the seed is a uint64 and the draw a uint32")
+        ids = np.arange(T, dtype=np.uint32) if tensor_ids is None else np.ascontiguousarray(tensor_ids, dtype=np.uint32)
+        if ids.shape != (T,):
+            raise ValueError("one stream id per tensor is required")
+        dt = tensors[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the clip-and-noise pass takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        iptr = np.zeros(T, dtype=np.uint64)
+        optr = np.zeros(T, dtype=np.uint64)
+        numels = np.zeros(T, dtype=np.int64)
+        for t, (x, o) in enumerate(zip(tensors, outs)):
+            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"tensor {t}: a contiguous {dt} tensor on {self.device} is required")
+            if o.dtype != dt or o.device != self.device or not o.is_contiguous() or o.numel() != x.numel():
+                raise ValueError(f"output {t}: a contiguous {dt} tensor of {x.numel()} elements on {self.device} "
+                                 "is required")
+            n = x.numel()
+            iptr[t] = x.data_ptr() if n else 0
+            optr[t] = o.data_ptr() if n else 0
+            numels[t] = n
+        _native.check(
+            self._lib.fedavg_dp_noise(
+                self._h, DTYPE_CODES[dt], iptr.ctypes.data, numels.ctypes.data, ids.ctypes.data, T, optr.ctypes.data,
+                int(row_len), float(C), float(noise_scale), int(seed), int(draw), self.stream,
+            )
+        )
+
     def sparse_index_errors(self) -> bool:
         """Wait for the stream and report (once) whether a sparse fold since the last report met an
         index violation (``fedavg_sparse_index_errors``)."""

@@ -147,7 +147,10 @@ int32_t fedavg_build_flags(void);
  * "route_chunk" (wanted ids per workgroup of the rank walk), "route_threads", "route_max_sources" and
  * "route_max_node_space" of fedavg_route_rows;
  * "quant_tile" (elements per workgroup), "quant_threads" and "quant_per_lane" (consecutive elements a
- * lane encodes) of fedavg_quant_encode.
+ * lane encodes) of fedavg_quant_encode;
+ * "dp_tile" (elements per piece of a sum and per workgroup of the apply pass), "dp_threads" (lanes
+ * that share a piece) and "dp_ae_<d>" (elements of one 16-byte group: what a lane adds in a row) of
+ * fedavg_dp_noise.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -718,6 +721,93 @@ int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const void* const* i
                             const uint32_t* tensor_ids /* [T], host, or NULL: 0 .. T - 1 */,
                             int32_t num_tensors, void* const* record_ptrs /* [T], device */,
                             int32_t level, double weight, uint64_t seed, uint32_t draw, void* stream);
+
+/*
+ * The clip-and-noise pass of the differential-privacy endpoints: the arithmetic of the reference's
+ * add_dp_noise / add_dp_noise_to_parameter (simulation_lib/dp.py:13-47) on num_tensors device tensors
+ * of one dtype (FEDAVG_F32 / F16 / BF16 / F64) where they lie. The contract is DESIGN.md §5r, restated
+ * independently in tests/dp_reference.py.
+ *
+ * in_ptrs[num_tensors] (host array of device pointers): tensor t holds numels[t] (host, >= 0)
+ * elements, aligned to the element only (NULL allowed where numels[t] == 0). out_ptrs[num_tensors]:
+ * buffers of the same dtype and sizes; out_ptrs[t] == in_ptrs[t] is allowed (an element is read and
+ * then written by the same lane), any other overlap is not. Nothing outside the outputs is written.
+ *   row_len == 0: all tensors together are one vector with one norm (add_dp_noise_to_parameter).
+ *   row_len > 0:  num_tensors == 1 and numels[0] % row_len == 0; every row of row_len elements has its
+ *                 own norm (add_dp_noise on a 2-D+ tensor; a 1-D tensor is one row).
+ * noise_scale is the fp64 product sigma * C, formed by the caller.
+ *
+ * Every line is one separately rounded fp64 operation after the exact widening of the element: no
+ * FMA, no reciprocal, IEEE division, the correctly rounded square root.
+ *   q = x * x;  acc = acc + q                                 (the sum of squares, from +0.0)
+ *   norm = sqrt(acc);  t = norm / C;  s = (t < 1) ? 1 : t     (a NaN t stays NaN)
+ *   y = x / s;  n = z * noise_scale;  o = y + n;  out = o rounded once, to nearest even, into the dtype
+ * (so with noise_scale == 0 a zero comes back with the sign of y + z * 0: -0.0 only where x is -0.0
+ * and z < 0).
+ *
+ * The order of the sum. G = "dp_ae_<d>", Tl = "dp_tile". A sum (whole-list mode: the one sum; row
+ * mode: a row's) is cut into pieces of Tl elements: whole-list mode cuts every tensor from its first
+ * element (a tensor's last piece is shorter, an empty tensor has none) and takes the pieces of all
+ * tensors in list order; row mode cuts every row from its first element. A piece's partial: with
+ * its elements in groups of G consecutive ones (group 0 starts at the piece's start), lane j of
+ * "dp_threads" = 256 adds the squares of groups j, j + 256, ... in increasing element index, from
+ * +0.0 (a lane without elements holds +0.0); the 256 lane sums combine by the adjacent-pair tree:
+ * v[j] = v[2j] + v[2j + 1], eight times. The sum: lane j adds the partials j, j + 256, ... of its
+ * pieces in increasing index from +0.0, and the same tree combines the lanes. The order depends on
+ * numels, row_len and the dtype's G alone. All terms are >= 0: any order is within
+ * (P + 2) * 2^-53 relative of the exact sum of P terms.
+ *
+ * z is element i's normal deviate of tensor t: the Philox4x32-10 block of fedavg_quant_encode's fp64
+ * stream, key (seed & 0xffffffff, seed >> 32), counter (block & 0xffffffff, block >> 32, id, draw),
+ * block = i / 2, id = tensor_ids[t] (tensor_ids == NULL: id = t); in row mode i counts through the
+ * whole tensor. With the output words w0..w3:
+ *   a = (w1 >> 5) * 2^26 + (w0 >> 6);  b = (w3 >> 5) * 2^26 + (w2 >> 6)          (53-bit integers)
+ *   u1 = (a + 1) * 2^-53 in (0, 1];  u2 = b * 2^-53 in [0, 1)
+ *   r = sqrt(-2 * LN(u1));  z[2 block] = r * COS(u2);  z[2 block + 1] = r * SIN(u2)
+ * LN, COS and SIN are the sequences below: each line one rounded fp64 + - * /, no FMA, no library
+ * function; integer steps where marked. Constants are hex floats.
+ *   LN(u1), v = a + 1:
+ *     d = (double)v (exact); E = d's unbiased exponent, F = d's 52 fraction bits     (integer)
+ *     up = F >= 0x6a09e667f3bcd;  e = E - 53 + up;  m = the double with fraction F and unbiased
+ *     exponent -up, in [sqrt(1/2), sqrt(2))                                          (integer)
+ *     f = m - 1;  g = 2 + f;  s = f / g;  w = s * s
+ *     p = L10;  then for k = 9 .. 1:  p = p * w;  p = p + Lk;    then  p = p * w;  p = p * s
+ *     q = s + p;  lm = q + q;  el = (double)e * 0x1.62e42fefa39efp-1;  LN = el + lm
+ *     L1..L10 = 1/3 .. 1/21 = 0x1.5555555555555p-2, 0x1.999999999999ap-3, 0x1.2492492492492p-3,
+ *       0x1.c71c71c71c71cp-4, 0x1.745d1745d1746p-4, 0x1.3b13b13b13b14p-4, 0x1.1111111111111p-4,
+ *       0x1.e1e1e1e1e1e1ep-5, 0x1.af286bca1af28p-5, 0x1.8618618618618p-5
+ *     t = LN * -2;  r = sqrt(t)           (LN <= 0; u1 = 1 gives LN = +0.0, t = -0.0, r = -0.0)
+ *   COS(u2), SIN(u2): k = b >> 50 (the octant), fi = b mod 2^50, gi = k odd ? 2^50 - fi : fi (integer)
+ *     g = (double)gi * 2^-50 (exact);  x = g * 0x1.921fb54442d18p-1;  w = x * x
+ *     p = S8;  then for k = 7 .. 1:  p = p * w;  p = p + Sk;    then  p = p * w;  p = p * x;  sn = x + p
+ *     c = C8;  then for k = 7 .. 1:  c = c * w;  c = c + Ck;    then  c = c * w;  cs = 1 + c
+ *     S1..S8 = -1/3!, 1/5!, .., 1/17! = -0x1.5555555555555p-3, 0x1.1111111111111p-7,
+ *       -0x1.a01a01a01a01ap-13, 0x1.71de3a556c734p-19, -0x1.ae64567f544e4p-26, 0x1.6124613a86d09p-33,
+ *       -0x1.ae7f3e733b81fp-41, 0x1.952c77030ad4ap-49
+ *     C1..C8 = -1/2!, 1/4!, .., 1/16! = -0x1p-1, 0x1.5555555555555p-5, -0x1.6c16c16c16c17p-10,
+ *       0x1.a01a01a01a01ap-16, -0x1.27e4fb7789f5cp-22, 0x1.1eed8eff8d898p-29, -0x1.93974a8c07c9dp-37,
+ *       0x1.ae7f3e733b81fp-45
+ *     k = 1, 2, 5, 6: COS = sn, SIN = cs; else COS = cs, SIN = sn; then COS is negated (its sign bit
+ *     flipped) for k = 2..5 and SIN for k = 4..7.
+ *
+ * Three launches whatever num_tensors is (the piece partials, one s per row or one in all, the apply
+ * pass over tiles of Tl elements that start at even indices of their tensor, so no pair belongs to
+ * two workgroups), no atomics, no host round trip: asynchronous on `stream`. The result depends on
+ * the inputs and the arguments alone. The accumulator and its state are not touched. A call's
+ * partials and s values live in the context: calls on one context are ordered by their stream.
+ * A non-finite input element latches FEDAVG_FLAG_INPUT_NAN (fedavg_check reports
+ * FEDAVG_ERR_NAN_INPUT); the outputs of such a call are unspecified but stay inside their buffers.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype; a NULL table; num_tensors < 1 or >
+ * 2^20; a negative count; a NULL input or output where numel > 0, or one not aligned to its element;
+ * a C that is not finite and > 0; a noise_scale that is not finite and >= 0; a negative row_len, one
+ * that does not divide the tensor, or row_len > 0 with num_tensors != 1; more than 2^31 - 1 tiles),
+ * FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_dp_noise(fedavg_ctx* ctx, int32_t dtype, const void* const* in_ptrs /* [T], device */,
+                        const int64_t* numels /* [T], host */,
+                        const uint32_t* tensor_ids /* [T], host, or NULL: 0 .. T - 1 */, int32_t num_tensors,
+                        void* const* out_ptrs /* [T], device */, int64_t row_len, double C, double noise_scale,
+                        uint64_t seed, uint32_t draw, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
