@@ -46,7 +46,7 @@ from .message import (
     get_message_size,
 )
 from .quantized import BroadcastQuantizer, philox_uniforms
-from .sparse import SparseDelta, topk_sparsify
+from .sparse import SparseDelta, TopKErrorFeedback, TopKSparseEndpoint, topk_sparsify, topk_sparsify_parameter
 
 __all__ = [
     "AggregationAlgorithm",
@@ -80,6 +80,8 @@ __all__ = [
     "ServerOptFedAVGAlgorithm",
     "SparseDelta",
     "SparseFedAVGAlgorithm",
+    "TopKErrorFeedback",
+    "TopKSparseEndpoint",
     "add_dp_noise",
     "add_dp_noise_to_parameter",
     "compute_dp_sigma",
@@ -87,6 +89,7 @@ __all__ = [
     "normal_stream",
     "philox_uniforms",
     "topk_sparsify",
+    "topk_sparsify_parameter",
 ]
 
 
@@ -211,6 +214,18 @@ def _register_builtin() -> None:
             server_cls=AggregationServer,
             client_endpoint_cls=DifferentialPrivacyParameterEndpoint,
             algorithm_cls=FedAVGAlgorithm,
+        )
+    # sparse FedAvg whose workers sparsify their diffs before sending (top-k with error feedback): the
+    # sparse rule behind the top-k client endpoint
+    if not AlgorithmRepository.has_algorithm("fed_avg_sparse_topk"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_avg_sparse_topk",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            client_endpoint_cls=TopKSparseEndpoint,
+            algorithm_cls=SparseFedAVGAlgorithm,
         )
 
 

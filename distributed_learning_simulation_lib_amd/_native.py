@@ -150,6 +150,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_dp_noise": (
         c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_double, c_double,
                   ctypes.c_uint64, c_uint32, c_void_p]),
+    # the client-side top-k step with error feedback (topk_kernels.hip); tables as raw addresses
+    "fedavg_topk_sparsify": (
+        c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                  c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

@@ -22,7 +22,7 @@ LIB_PATH = LIB_DIR / LIB_NAME
 SOURCES = [CSRC / "fedavg_kernels.hip", CSRC / "personalized_kernels.hip", CSRC / "robust_kernels.hip",
            CSRC / "krum_kernels.hip", CSRC / "point_kernels.hip", CSRC / "clip_kernels.hip", CSRC / "trust_kernels.hip",
            CSRC / "opt_kernels.hip", CSRC / "sparse_kernels.hip", CSRC / "route_kernels.hip", CSRC / "quant_kernels.hip",
-           CSRC / "dp_kernels.hip",
+           CSRC / "dp_kernels.hip", CSRC / "topk_kernels.hip",
            CSRC / "call_tables.cpp", CSRC / "host_pack.cpp", CSRC / "sharded_comm.cpp", CSRC / "multi_device.cpp"]
 HEADERS = [REPO_DIR / "include" / "fedavg_hip.h", *sorted(CSRC.glob("*.h"))]
 # C++ clients of the ABI alone (no Python, no torch), built next to the library

@@ -79,6 +79,29 @@ __device__ __forceinline__ u32x4 load_guarded(const void* base, int64_t elem, in
   return raw;
 }
 
+// The counterpart of load_guarded: only elements below `have` of the 16-byte image are written.
+template <typename T>
+__device__ __forceinline__ void store_guarded(void* base, int64_t elem, int have, const u32x4& raw) {
+  constexpr int N = Format<T>::N;
+  if constexpr (sizeof(T) == 2) {
+    uint16_t FEDAVG_AS_GLOBAL* p = (uint16_t FEDAVG_AS_GLOBAL*)base + elem;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      if (i < have) p[i] = static_cast<uint16_t>(raw[i / 2] >> (16 * (i % 2)));
+    }
+  } else {
+    constexpr int W = sizeof(T) / 4;
+    uint32_t FEDAVG_AS_GLOBAL* p = (uint32_t FEDAVG_AS_GLOBAL*)base + elem * W;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      if (i < have) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) p[i * W + w] = raw[i * W + w];
+      }
+    }
+  }
+}
+
 // N fp64 values of a point segment (a centre, a direction) from element `elem`: only elements below
 // `have` are read, the rest stay +0.0, and a NULL base is the origin; 16-byte loads where `vec` says
 // the segment is 16-byte aligned.

@@ -3007,6 +3007,7 @@ const SideModule kSideModules[FEDAVG_MODULES] = {
     {fedavg_internal_route_constant, nullptr},
     {fedavg_internal_quant_constant, fedavg_internal_quant_release},
     {fedavg_internal_dp_constant, fedavg_internal_dp_release},
+    {fedavg_internal_topk_constant, fedavg_internal_topk_release},
 };
 
 bool side_constant(const char* name, int64_t* v) {

@@ -22,6 +22,7 @@ enum fedavg_module {
   FEDAVG_MODULE_ROUTE,
   FEDAVG_MODULE_QUANT,
   FEDAVG_MODULE_DP,
+  FEDAVG_MODULE_TOPK,
   FEDAVG_MODULES
 };
 
@@ -52,6 +53,7 @@ FEDAVG_INTERNAL int32_t fedavg_internal_sparse_constant(const char* name, int64_
 FEDAVG_INTERNAL int32_t fedavg_internal_route_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL int32_t fedavg_internal_quant_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL int32_t fedavg_internal_dp_constant(const char* name, int64_t* out);
+FEDAVG_INTERNAL int32_t fedavg_internal_topk_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL void fedavg_internal_robust_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_krum_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_point_release(int32_t device, void* state);
@@ -61,3 +63,4 @@ FEDAVG_INTERNAL void fedavg_internal_opt_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_sparse_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_quant_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_dp_release(int32_t device, void* state);
+FEDAVG_INTERNAL void fedavg_internal_topk_release(int32_t device, void* state);

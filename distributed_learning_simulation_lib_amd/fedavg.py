@@ -1244,6 +1244,51 @@ class FedAvgContext:
             )
         )
 
+    def topk_sparsify(self, deltas: Sequence[torch.Tensor], errors: Sequence[torch.Tensor | None] | None,
+                      keeps: Sequence[int], indices: Sequence[torch.Tensor], values: Sequence[torch.Tensor],
+                      residuals: Sequence[torch.Tensor]) -> None:
+        """The top-k step with error feedback on ``deltas`` (contiguous tensors of one floating dtype
+        on the context's device, of any sizes: the context's layout plays no part) in a fixed number
+        of launches (``fedavg_topk_sparsify``): tensor ``t`` sends the ``keeps[t]``
+        entries of largest magnitude of ``deltas[t] + errors[t]`` (``errors`` or an entry of it may
+        be ``None``: no residual yet), ties to the lower index, as ascending int32 ``indices[t]`` and
+        ``values[t]`` (``keeps[t]`` entries each), and leaves what it did not send in
+        ``residuals[t]``, which may be ``errors[t]`` or ``deltas[t]`` itself. Asynchronous."""
+        T = len(deltas)
+        if T == 0 or not (len(keeps) == len(indices) == len(values) == len(residuals) == T) or (
+                errors is not None and len(errors) != T):
+            raise ValueError("one keep count, index, value and residual tensor per delta and at least one delta "
+                             "are required")
+        dt = deltas[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the top-k step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        ptrs = np.zeros((5, T), dtype=np.uint64)  # delta, error, index, value, residual
+        counts = np.zeros((2, T), dtype=np.int64)  # numel, keep
+        for t in range(T):
+            x, n, k = deltas[t], deltas[t].numel(), int(keeps[t])
+            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"delta {t}: a contiguous {dt} tensor on {self.device} is required")
+            if not 0 <= k <= n:
+                raise ValueError(f"delta {t}: keeps {k} of {n} elements")
+            e = None if errors is None else errors[t]
+            for what, y, dty, size in (("error", e, dt, n), ("index", indices[t], torch.int32, k),
+                                       ("value", values[t], dt, k), ("residual", residuals[t], dt, n)):
+                if y is not None and (y.dtype != dty or y.device != self.device or not y.is_contiguous()
+                                      or y.numel() != size):
+                    raise ValueError(f"{what} {t}: a contiguous {dty} tensor of {size} elements on {self.device} "
+                                     "is required")
+            ptrs[:, t] = (x.data_ptr() if n else 0, e.data_ptr() if e is not None and n else 0,
+                          indices[t].data_ptr() if k else 0, values[t].data_ptr() if k else 0,
+                          residuals[t].data_ptr() if n else 0)
+            counts[:, t] = (n, k)
+        _native.check(
+            self._lib.fedavg_topk_sparsify(
+                self._h, DTYPE_CODES[dt], ptrs[0].ctypes.data, ptrs[1].ctypes.data if errors is not None else None,
+                counts[0].ctypes.data, counts[1].ctypes.data, T, ptrs[2].ctypes.data, ptrs[3].ctypes.data,
+                ptrs[4].ctypes.data, self.stream,
+            )
+        )
+
     def sparse_index_errors(self) -> bool:
         """Wait for the stream and report (once) whether a sparse fold since the last report met an
         index violation (``fedavg_sparse_index_errors``)."""

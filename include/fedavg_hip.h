@@ -150,7 +150,10 @@ int32_t fedavg_build_flags(void);
  * lane encodes) of fedavg_quant_encode;
  * "dp_tile" (elements per piece of a sum and per workgroup of the apply pass), "dp_threads" (lanes
  * that share a piece) and "dp_ae_<d>" (elements of one 16-byte group: what a lane adds in a row) of
- * fedavg_dp_noise.
+ * fedavg_dp_noise;
+ * "topk_tile" (elements per workgroup of the write pass: the unit of the per-tile counts),
+ * "topk_chunk" (consecutive tiles per workgroup of the histogram and count passes) and
+ * "topk_threads" of fedavg_topk_sparsify.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -808,6 +811,48 @@ int32_t fedavg_dp_noise(fedavg_ctx* ctx, int32_t dtype, const void* const* in_pt
                         const uint32_t* tensor_ids /* [T], host, or NULL: 0 .. T - 1 */, int32_t num_tensors,
                         void* const* out_ptrs /* [T], device */, int64_t row_len, double C, double noise_scale,
                         uint64_t seed, uint32_t draw, void* stream);
+
+/*
+ * The client-side top-k step with error feedback (the `_sparsify` of the reference's
+ * worker/error_feedback_worker.py with top-k as the scheme) on num_tensors device tensors of one dtype
+ * (FEDAVG_F32 / F16 / BF16 / F64) where they lie: what sparse.topk_sparsify computes per tensor. The
+ * contract is DESIGN.md §5s; the oracle is the CPU path of sparse.topk_sparsify.
+ *
+ * Tensor t holds numels[t] (host, 0 .. 2^31 - 1) elements at delta_ptrs[t], aligned to the element
+ * only, and sends keeps[t] (host, 0 .. numels[t]) of them. error_ptrs (NULL: no tensor has a residual
+ * yet) holds per tensor its residual of the same size and dtype, or NULL.
+ *   total[e] = delta[e] + error[e], the IEEE sum rounded once to nearest even into the dtype (for
+ *              fp16 / bf16 the fp32 sum rounded to the dtype, which is the same value); without an
+ *              error total[e] is delta[e] bit for bit.
+ *   key[e]   = the bits of total[e] with the sign cleared, as an unsigned integer; every NaN has the
+ *              one largest key. So +0.0 and -0.0 tie, inf beats every finite value, NaNs tie above inf.
+ *   S        = the keeps[t] elements of largest (key, -index): among equal keys the lower index wins.
+ *   index_ptrs[t][j] = the j-th element of S in increasing order (int32); value_ptrs[t][j] =
+ *   total[index_ptrs[t][j]] bit for bit; residual_ptrs[t][e] = +0.0 for e in S, total[e] otherwise.
+ * residual_ptrs[t] may be error_ptrs[t] or delta_ptrs[t] (every element is read and then written by
+ * the same lane in the first pass); no other overlap is allowed. index_ptrs[t] and value_ptrs[t] hold
+ * keeps[t] entries (NULL allowed where keeps[t] == 0, as the others are where numels[t] == 0).
+ * Nothing outside the outputs is written.
+ *
+ * No sort: a radix select over the key's digits from the top (fp32 11 + 10 + 10 bits, fp16 / bf16
+ * 8 + 7, fp64 11 + 11 + 11 + 10 + 10 + 10) finds per tensor the threshold key, then a count per tile
+ * of "topk_tile" elements, a scan over each tensor's tiles and an order-preserving write. 2 launches
+ * per digit and 3 more (fp32 9, fp16 / bf16 7, fp64 15) whatever num_tensors is, one grid over the
+ * tiles of all tensors; no atomics on global memory, no floating-point reduction, no host round trip:
+ * asynchronous on `stream`. The result depends on the inputs alone. The accumulator, its state and
+ * the NaN flags are not touched. A call's histograms, select states and tile counts live in the
+ * context (8 KiB per chunk of "topk_chunk" tiles): calls on one context are ordered by their stream.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype; a NULL table other than error_ptrs;
+ * num_tensors < 1 or > 2^20; a negative count; keeps[t] > numels[t]; numels[t] > 2^31 - 1; a NULL
+ * delta or residual where numel > 0, a NULL index or value buffer where keep > 0, or a buffer not
+ * aligned to its element; more than 2^31 - 1 tiles), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_topk_sparsify(fedavg_ctx* ctx, int32_t dtype, const void* const* delta_ptrs /* [T], device */,
+                             const void* const* error_ptrs /* [T], device, or NULL; entries may be NULL */,
+                             const int64_t* numels /* [T], host */, const int64_t* keeps /* [T], host */,
+                             int32_t num_tensors, int32_t* const* index_ptrs /* [T], device */,
+                             void* const* value_ptrs /* [T], device */, void* const* residual_ptrs /* [T], device */,
+                             void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
