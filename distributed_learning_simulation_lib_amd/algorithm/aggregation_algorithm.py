@@ -18,7 +18,7 @@ from typing import Any
 import torch
 
 from ..fedavg import ClientTable, FedAvgContext, ModelLayout
-from ..message import Message, ModelParameter, is_parameter_message
+from ..message import Message, ModelParameter, is_parameter_message, wire_class
 from ..quantized import QuantizedTensor, dequantize_tensor
 
 # (device index, layout, split policy) -> context, for the class-level weighted_avg
@@ -72,6 +72,15 @@ def split_empty(layout: ModelLayout) -> tuple[ModelLayout | None, list[int]]:
     return ModelLayout(
         names=tuple(layout.names[i] for i in keep), shapes=tuple(layout.shapes[i] for i in keep)
     ), keep
+
+
+def fill_empty(layout: ModelLayout, result: ModelParameter, dtype: torch.dtype, device: torch.device) -> ModelParameter:
+    """``result`` in layout order, with an empty tensor for every name it lacks: the zero-element
+    tensors that ``split_empty`` kept out of the native layout."""
+    for i, name in enumerate(layout.names):
+        if name not in result:
+            result[name] = torch.empty(layout.shapes[i], dtype=dtype, device=device)
+    return {name: result[name] for name in layout.names}
 
 
 class AggregationAlgorithm(ABC):
@@ -183,10 +192,7 @@ class AggregationAlgorithm(ABC):
             ctx.raise_on_nan([(table, dt)])
             for j, i in enumerate(keep):
                 result[layout.names[i]] = outs[j].view(layout.shapes[i])
-        for i, name in enumerate(layout.names):
-            if i not in keep:
-                result[name] = torch.empty(layout.shapes[i], dtype=torch.float64, device=device)
-        return {name: result[name] for name in layout.names}
+        return fill_empty(layout, result, torch.float64, device)
 
     # ---- plugin protocol (aggregation_algorithm.py:93-112) ----------------------------------
     def process_worker_data(
@@ -202,6 +208,53 @@ class AggregationAlgorithm(ABC):
 
     @abstractmethod
     def aggregate_worker_data(self) -> Any: ...
+
+    def _result_message(self, parameter: ModelParameter) -> Any:
+        """The round's answer: ``parameter`` with the reduced ``other_data`` (and the losses, where
+        ``aggregate_loss`` is set), as the first message's own ``ParameterMessage`` class — the
+        reference server matches the result with ``case ParameterMessageBase()``
+        (aggregation_server.py:87) and caches it (:148-167)."""
+        other_data: dict[str, Any] = {}
+        if self.aggregate_loss:
+            other_data |= self._aggregate_loss(self._all_worker_data)
+        other_data |= self._check_and_reduce_other_data(self._all_worker_data)
+        first = next(iter(self._all_worker_data.values()))
+        return wire_class(first, "ParameterMessage")(
+            parameter=parameter,
+            end_training=first.end_training,
+            in_round=first.in_round,
+            other_data=other_data,
+        )
+
+    @classmethod
+    def _aggregate_loss(cls, all_worker_data: MutableMapping[int, Message]) -> dict[str, Any]:
+        """Ratio-weighted training/validation loss (fed_avg_algorithm.py:115-134)."""
+        assert all_worker_data
+        first = next(iter(all_worker_data.values()))
+        loss_types = [t for t in ("training_loss", "validation_loss") if t in first.other_data]
+        ratios = AggregationAlgorithm.get_ratios(all_worker_data)
+        loss_dict = {
+            t: AggregationAlgorithm.weighted_avg_for_scalar(all_worker_data, ratios, scalar_key=t)
+            for t in loss_types
+        }
+        assert loss_dict
+        for msg in all_worker_data.values():
+            for t in ("training_loss", "validation_loss"):
+                msg.other_data.pop(t, None)
+        return loss_dict
+
+    @classmethod
+    def _check_and_reduce_other_data(cls, all_worker_data: MutableMapping[int, Message]) -> dict[str, Any]:
+        """Every client must agree on every other_data key (fed_avg_algorithm.py:136-149).
+        ``PersonalizedFedAVGAlgorithm`` has a static method of this name over a list of messages: that
+        class assembles one message per receiver itself and does not call ``_result_message``."""
+        merged: dict[str, Any] = {}
+        for msg in all_worker_data.values():
+            for k, v in msg.other_data.items():
+                if k in merged and v != merged[k]:
+                    raise RuntimeError(f"different values on key {k}")
+                merged.setdefault(k, v)
+        return merged
 
     def clear_worker_data(self) -> None:
         self._all_worker_data.clear()

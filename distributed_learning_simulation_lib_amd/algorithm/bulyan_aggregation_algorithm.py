@@ -36,24 +36,15 @@ quantised payloads are refused as Krum refuses them.
 
 from __future__ import annotations
 
-from typing import Any, NamedTuple
+from typing import NamedTuple
 
 import torch
 
-from ..fedavg import ClientTable, ModelLayout, NaNAggregationError, bulyan_select, out_code
+from ..fedavg import NaNAggregationError, bulyan_select
 from .._native import KRUM_MAX_CLIENTS, ROBUST_MAX_CLIENTS
-from ..message import KIND_DELTA, KIND_PARAMETER, Message, ModelParameter, message_kind, wire_class
-from ..quantized import QuantizedTensor
-from .aggregation_algorithm import (
-    AggregationAlgorithm,
-    context_for,
-    default_device,
-    split_empty,
-    to_device_operand,
-    unify_dtype,
-)
-from .fed_avg_algorithm import FedAVGAlgorithm
-from .krum_aggregation_algorithm import pairwise_sqdist_cpu
+from ..message import ModelParameter
+from .aggregation_algorithm import fill_empty
+from .dense_round import DenseRoundAlgorithm, _GpuRound, pairwise_sqdist_cpu
 from .robust_aggregation_algorithm import _total_order_sort
 
 
@@ -93,70 +84,22 @@ def mean_around_median_cpu(tensors: list[torch.Tensor], keep: int) -> torch.Tens
     return out
 
 
-class BulyanFedAVGAlgorithm(AggregationAlgorithm):
+class BulyanFedAVGAlgorithm(DenseRoundAlgorithm):
     """``num_byzantine`` is f, the assumed number of Byzantine clients (``None``: the most the
     round's client count allows, ``(n - 3) // 4``); ``out_dtype`` float64 (what the reference's
     algorithms return) or float32 (that result rounded to nearest even); ``device`` a GPU (default:
     the current one) or the CPU."""
 
-    accepts_delta_messages = False
-    accepts_quantized_messages = False
+    rule_subject = rule_name = "Bulyan"
+    shape_error_names_client = True  # and no max_clients: _rule refuses too few clients before too many
 
     def __init__(self, num_byzantine: int | None = None, device: torch.device | str | None = None,
                  out_dtype: torch.dtype = torch.float64) -> None:
-        super().__init__()
         if num_byzantine is not None and int(num_byzantine) < 0:
             raise ValueError(f"num_byzantine must be >= 0, not {num_byzantine}")
-        out_code(out_dtype)  # TypeError for anything but float32 / float64
+        super().__init__(device, out_dtype)
         self.num_byzantine = None if num_byzantine is None else int(num_byzantine)
-        self.out_dtype = out_dtype
-        self.aggregate_loss: bool = False
         self.last_selection: BulyanSelection | None = None
-        self.__device = torch.device(device) if device is not None else None
-
-    @property
-    def device(self) -> torch.device:
-        if self.__device is None:
-            self.__device = default_device()
-        if self.__device.type == "cuda" and self.__device.index is None:
-            self.__device = torch.device("cuda", torch.cuda.current_device())
-        return self.__device
-
-    def process_worker_data(self, worker_id: int, worker_data: Message | None) -> bool:
-        if worker_data is not None:
-            kind = message_kind(worker_data)
-            if kind == KIND_DELTA:
-                raise NotImplementedError(
-                    "Bulyan needs full updates: restore a DeltaParameterMessage first "
-                    "(accepts_delta_messages is False, so this package's server does)")
-            if kind != KIND_PARAMETER:
-                raise TypeError(f"Bulyan takes ParameterMessage updates, not {type(worker_data).__name__}")
-            if any(isinstance(t, QuantizedTensor) for t in worker_data.parameter.values()):
-                raise NotImplementedError(
-                    "Bulyan reads dense tensors: dequantise QSGD / NNADQ payloads first "
-                    "(accepts_quantized_messages is False, so this package's server does)")
-        return super().process_worker_data(worker_id, worker_data)
-
-    # ---- end of round ---------------------------------------------------------------------
-    def _rows(self) -> tuple[ModelLayout, list[int], list[list[torch.Tensor]]]:
-        """The layout (names in first-seen order), the worker ids in arrival order and, per worker,
-        its tensors in layout order; ValueError for a client that lacks a key or differs in shape."""
-        assert self._all_worker_data
-        shapes: dict[str, tuple[int, ...]] = {}
-        for wid, msg in self._all_worker_data.items():
-            assert msg.parameter
-            for name, t in msg.parameter.items():
-                shape = shapes.setdefault(name, tuple(t.shape))
-                if tuple(t.shape) != shape:
-                    raise ValueError(f"client {wid}, tensor {name}: shape {tuple(t.shape)} differs from {shape}")
-        ids, rows = [], []
-        for wid, msg in self._all_worker_data.items():
-            for name in shapes:
-                if name not in msg.parameter:
-                    raise ValueError(f"client {wid} lacks tensor {name}: Bulyan compares whole updates")
-            ids.append(wid)
-            rows.append([msg.parameter[name] for name in shapes])
-        return ModelLayout(names=tuple(shapes), shapes=tuple(shapes.values())), ids, rows
 
     def _rule(self, n: int) -> tuple[int, int, int]:
         """(f, theta, beta) for a round of n clients; the refusals that need no data."""
@@ -188,46 +131,18 @@ class BulyanFedAVGAlgorithm(AggregationAlgorithm):
             chosen = self._select(pairwise_sqdist_cpu(rows), ids, f)
             return {name: mean_around_median_cpu([rows[r][i] for r in chosen], beta).to(self.out_dtype)
                     for i, name in enumerate(layout.names)}
-        native, keep = split_empty(layout)
+        work = _GpuRound(layout, rows, device, [1.0] * len(ids))
         result: ModelParameter = {}
-        if native is None:
+        if work.native is None:
             self._select(torch.zeros((len(ids), len(ids)), dtype=torch.float64), ids, f)
         else:
-            T = len(keep)
-            flat = [to_device_operand(rows[k][i], device) for k in range(len(ids)) for i in keep]
-            flat, dt = unify_dtype(flat)
-            flat = [t.contiguous() for t in flat]
-            table = ClientTable(T)
-            for k in range(len(ids)):
-                table.add_client(flat[k * T:(k + 1) * T], [1.0] * T)
-            ctx = context_for(native, device)
-            D = ctx.pairwise_sqdist(table, dt).cpu()  # the copy synchronises: the flags are final
-            ctx.raise_on_nan([(table, dt)])
-            chosen = self._select(D, ids, f)
-            picked = ClientTable(T)
-            for r in chosen:
-                picked.add_client(flat[r * T:(r + 1) * T], [1.0] * T)
-            outs = [torch.empty(n, dtype=self.out_dtype, device=device) for n in native.numels]
+            ctx, dt = work.ctx, work.dt
+            D = ctx.pairwise_sqdist(work.table, dt).cpu()  # the copy synchronises: the flags are final
+            ctx.raise_on_nan([(work.table, dt)])
+            picked = work.table_of(self._select(D, ids, f))
+            outs = [torch.empty(n, dtype=self.out_dtype, device=device) for n in work.native.numels]
             ctx.mean_around_median(picked, dt, beta, outs, self.out_dtype)
             ctx.raise_on_nan([(picked, dt)])
-            for j, i in enumerate(keep):
+            for j, i in enumerate(work.segments):
                 result[layout.names[i]] = outs[j].view(layout.shapes[i])
-        for i, name in enumerate(layout.names):
-            if name not in result:
-                result[name] = torch.empty(layout.shapes[i], dtype=self.out_dtype, device=device)
-        return {name: result[name] for name in layout.names}
-
-    def aggregate_worker_data(self) -> Any:
-        parameter = self._aggregate_parameter()
-        other_data: dict[str, Any] = {}
-        # the same message fields as KrumFedAVGAlgorithm / FedAVGAlgorithm.aggregate_worker_data
-        if self.aggregate_loss:
-            other_data |= FedAVGAlgorithm._FedAVGAlgorithm__aggregate_loss(self._all_worker_data)
-        other_data |= FedAVGAlgorithm._FedAVGAlgorithm__check_and_reduce_other_data(self._all_worker_data)
-        first = next(iter(self._all_worker_data.values()))
-        return wire_class(first, "ParameterMessage")(
-            parameter=parameter,
-            end_training=first.end_training,
-            in_round=first.in_round,
-            other_data=other_data,
-        )
+        return fill_empty(layout, result, self.out_dtype, device)

@@ -54,7 +54,6 @@ from ..message import (
     ModelParameter,
     ParameterMessage,
     message_kind,
-    wire_class,
 )
 from ..quantized import QuantizedTensor, dequantize_tensor, record_layout
 from .dynamic_wave import DynamicWave, PluginSettings
@@ -1269,20 +1268,7 @@ class FedAVGAlgorithm(AggregationAlgorithm):
         return tot.to(torch.float32) if self.__tot_fp32.get(name) else tot.clone()
 
     def aggregate_worker_data(self) -> ParameterMessage:
-        parameter = self._aggregate_parameter()
-        other_data: dict[str, Any] = {}
-        if self.aggregate_loss:
-            other_data |= self.__aggregate_loss(self._all_worker_data)
-        other_data |= self.__check_and_reduce_other_data(self._all_worker_data)
-        first = next(iter(self._all_worker_data.values()))
-        # the caller's own ParameterMessage class: the reference server matches the result
-        # with `case ParameterMessageBase()` (aggregation_server.py:87) and caches it (:148-167)
-        return wire_class(first, "ParameterMessage")(
-            parameter=parameter,
-            end_training=first.end_training,
-            in_round=first.in_round,
-            other_data=other_data,
-        )
+        return self._result_message(self._aggregate_parameter())
 
     def clear_worker_data(self) -> None:
         super().clear_worker_data()
@@ -1307,31 +1293,3 @@ class FedAVGAlgorithm(AggregationAlgorithm):
         if self.__multi is not None:
             self.__multi.close()
             self.__multi = None
-
-    @classmethod
-    def __aggregate_loss(cls, all_worker_data: MutableMapping[int, Message]) -> dict[str, Any]:
-        """Ratio-weighted training/validation loss (fed_avg_algorithm.py:115-134)."""
-        assert all_worker_data
-        first = next(iter(all_worker_data.values()))
-        loss_types = [t for t in ("training_loss", "validation_loss") if t in first.other_data]
-        ratios = AggregationAlgorithm.get_ratios(all_worker_data)
-        loss_dict = {
-            t: AggregationAlgorithm.weighted_avg_for_scalar(all_worker_data, ratios, scalar_key=t)
-            for t in loss_types
-        }
-        assert loss_dict
-        for msg in all_worker_data.values():
-            for t in ("training_loss", "validation_loss"):
-                msg.other_data.pop(t, None)
-        return loss_dict
-
-    @classmethod
-    def __check_and_reduce_other_data(cls, all_worker_data: MutableMapping[int, Message]) -> dict[str, Any]:
-        """Every client must agree on every other_data key (fed_avg_algorithm.py:136-149)."""
-        merged: dict[str, Any] = {}
-        for msg in all_worker_data.values():
-            for k, v in msg.other_data.items():
-                if k in merged and v != merged[k]:
-                    raise RuntimeError(f"different values on key {k}")
-                merged.setdefault(k, v)
-        return merged

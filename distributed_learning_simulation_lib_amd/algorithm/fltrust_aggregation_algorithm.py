@@ -22,7 +22,7 @@ independently):
    update of squared norm 0 (``S_root = 0``, step 6) gives no direction: ``ValueError``.
 4. The centre ``v`` is the model given to ``set_old_parameter``, converted to float64 and moved to
    the device once per round (never set, or its keys or shapes differ from the layout: the
-   ``ValueError`` of ``ClippedFedAVGAlgorithm`` names the key).
+   ``ValueError`` of ``DenseRoundAlgorithm._previous`` names the key).
 5. The direction is ``g = x_root.to(float64) - v``: one IEEE subtract per element.
 6. ``T_i = sum_e (x_i[e] - v[e]) * g[e]`` and ``S_i = sum_e (x_i[e] - v[e])^2`` over the kept clients,
    the root among them, in one ``moments_about_point`` call: per element ``d = x - v``,
@@ -41,8 +41,8 @@ independently):
    in arrival order, ``r = acc / W``, ``out = v + r``, written in ``out_dtype`` (float32: that
    float64 result rounded to nearest even).
 9. ``last_trust`` records the round.
-10. On a CPU ``device`` the same rule runs in torch (``moments_about_point_cpu`` and the clipped
-    class's loop over the clients), so the class returns the same bits on the CPU and on the GPU.
+10. On a CPU ``device`` the same rule runs in torch (``moments_about_point_cpu`` and centred
+    clipping's loop over the clients), so the class returns the same bits on the CPU and on the GPU.
 
 The rule tolerates a majority of malicious clients, as long as the root update is honest. Limits: at
 most 1024 clients, dense full updates only — delta and quantised payloads are refused
@@ -52,19 +52,14 @@ restores or dequantises before handing an update over).
 
 from __future__ import annotations
 
-import math
-from typing import Any, NamedTuple
+from typing import NamedTuple
 
 import torch
 
-from ..fedavg import ModelLayout, NaNAggregationError, out_code, trust_coefficients
+from ..fedavg import ModelLayout, NaNAggregationError, trust_coefficients
 from .._native import POINT_MAX_CLIENTS
-from ..message import KIND_DELTA, KIND_PARAMETER, Message, ModelParameter, message_kind, wire_class
-from ..quantized import QuantizedTensor
-from .aggregation_algorithm import AggregationAlgorithm, default_device
-from .clipped_aggregation_algorithm import ClippedFedAVGAlgorithm, _CpuClipRound, _GpuClipRound
-from .fed_avg_algorithm import FedAVGAlgorithm
-from .geometric_median_algorithm import _DTYPE_TAGS
+from ..message import ModelParameter
+from .dense_round import _DTYPE_TAGS, DenseRoundAlgorithm, _CpuRound, _GpuRound, finite_screen
 
 # the kernel's geometry where the native library cannot be asked (§5i's)
 TRUST_DEFAULTS = {"trust_chunk": 4096, "trust_threads": 256,
@@ -158,7 +153,7 @@ def moments_about_point_cpu(rows: list[list[torch.Tensor]], centre: list[torch.T
     return out[0], out[1]
 
 
-class _CpuTrustRound(_CpuClipRound):
+class _CpuTrustRound(_CpuRound):
     def __init__(self, layout: ModelLayout, rows: list[list[torch.Tensor]], device: torch.device) -> None:
         super().__init__(layout, rows, device)
         self.all_rows = self.rows
@@ -174,7 +169,7 @@ class _CpuTrustRound(_CpuClipRound):
         return T.tolist(), S.tolist()
 
 
-class _GpuTrustRound(_GpuClipRound):
+class _GpuTrustRound(_GpuRound):
     def direction(self, root: int, centre: list[torch.Tensor]) -> list[torch.Tensor]:
         out = [torch.empty(s, dtype=torch.float64, device=self.device) for s in self.layout.shapes]
         if self.native is not None:
@@ -186,92 +181,37 @@ class _GpuTrustRound(_GpuClipRound):
     def moments(self, centre: list[torch.Tensor], direction: list[torch.Tensor]) -> tuple[list[float], list[float]]:
         if self.native is None:
             return [0.0] * self.n, [0.0] * self.n
-        z = [centre[i].reshape(-1) for i in self.segments]
-        g = [direction[i].reshape(-1) for i in self.segments]
-        T, S = self.ctx.moments_about_point(self.table, self.dt, z, g)
+        T, S = self.ctx.moments_about_point(self.table, self.dt, self._flat(centre), self._flat(direction))
         T, S = T.cpu(), S.cpu()  # the copy synchronises: the flags are final
         self.ctx.raise_on_nan([(self.table, self.dt)])
         return T.tolist(), S.tolist()
 
 
-class FLTrustFedAVGAlgorithm(AggregationAlgorithm):
+class FLTrustFedAVGAlgorithm(DenseRoundAlgorithm):
     """``root_worker`` is the id of the worker whose update is the server's own, trained on the root
     dataset (no default); ``out_dtype`` float64 or float32 (that result rounded to nearest even);
     ``device`` a GPU (default: the current one) or the CPU."""
 
-    accepts_delta_messages = False
-    accepts_quantized_messages = False
+    rule_subject = rule_name = "FLTrust"
+    max_clients = POINT_MAX_CLIENTS
 
     def __init__(self, root_worker: int, device: torch.device | str | None = None,
                  out_dtype: torch.dtype = torch.float64) -> None:
-        super().__init__()
         if isinstance(root_worker, bool) or int(root_worker) != root_worker:
             raise ValueError(f"root_worker must be a worker id (an integer), not {root_worker!r}")
-        out_code(out_dtype)  # TypeError for anything but float32 / float64
+        super().__init__(device, out_dtype)
         self.root_worker = int(root_worker)
-        self.out_dtype = out_dtype
-        self.aggregate_loss: bool = False
         self.last_trust: TrustRecord | None = None
-        self.__device = torch.device(device) if device is not None else None
-
-    @property
-    def device(self) -> torch.device:
-        if self.__device is None:
-            self.__device = default_device()
-        if self.__device.type == "cuda" and self.__device.index is None:
-            self.__device = torch.device("cuda", torch.cuda.current_device())
-        return self.__device
-
-    def process_worker_data(self, worker_id: int, worker_data: Message | None) -> bool:
-        if worker_data is not None:
-            kind = message_kind(worker_data)
-            if kind == KIND_DELTA:
-                raise NotImplementedError(
-                    "FLTrust needs full updates: restore a DeltaParameterMessage first "
-                    "(accepts_delta_messages is False, so this package's server does)")
-            if kind != KIND_PARAMETER:
-                raise TypeError(f"FLTrust takes ParameterMessage updates, not {type(worker_data).__name__}")
-            if any(isinstance(t, QuantizedTensor) for t in worker_data.parameter.values()):
-                raise NotImplementedError(
-                    "FLTrust reads dense tensors: dequantise QSGD / NNADQ payloads first "
-                    "(accepts_quantized_messages is False, so this package's server does)")
-        return super().process_worker_data(worker_id, worker_data)
-
-    # ---- end of round ---------------------------------------------------------------------
-    def _rows(self) -> tuple[ModelLayout, list[int], list[list[torch.Tensor]]]:
-        """The layout (names in first-seen order), the worker ids in arrival order and, per worker,
-        its tensors in layout order; ValueError for a client that lacks a key or differs in shape."""
-        assert self._all_worker_data
-        shapes: dict[str, tuple[int, ...]] = {}
-        for msg in self._all_worker_data.values():
-            assert msg.parameter
-            for name, t in msg.parameter.items():
-                shape = shapes.setdefault(name, tuple(t.shape))
-                if tuple(t.shape) != shape:
-                    raise ValueError(f"tensor {name}: shape {tuple(t.shape)} differs from {shape}")
-        ids, rows = [], []
-        for wid, msg in self._all_worker_data.items():
-            for name in shapes:
-                if name not in msg.parameter:
-                    raise ValueError(f"client {wid} lacks tensor {name}: FLTrust compares whole updates")
-            ids.append(wid)
-            rows.append([msg.parameter[name] for name in shapes])
-        if len(ids) > POINT_MAX_CLIENTS:
-            raise NotImplementedError(f"{len(ids)} clients: FLTrust takes at most {POINT_MAX_CLIENTS}")
-        return ModelLayout(names=tuple(shapes), shapes=tuple(shapes.values())), ids, rows
 
     def _aggregate_parameter(self) -> ModelParameter:
         layout, ids, rows = self._rows()
         if self.root_worker not in ids:
             raise ValueError(f"the root worker {self.root_worker} sent no update this round: FLTrust has no direction")
         device = self.device
-        previous = ClippedFedAVGAlgorithm._previous(self, layout, device)  # type: ignore[arg-type]
+        previous = self._previous(layout, device)
         work = (_GpuTrustRound if device.type == "cuda" else _CpuTrustRound)(layout, rows, device)
 
-        # the finite screen: a client whose squared norm is +inf is dropped for the round
-        norms = work.distances(None)
-        kept = [k for k, v in enumerate(norms) if v != math.inf]
-        dropped = [ids[k] for k, v in enumerate(norms) if v == math.inf]
+        kept, dropped = finite_screen(work, ids)  # a client whose squared norm is +inf is dropped for the round
         if self.root_worker in dropped:
             raise ValueError(f"the root worker {self.root_worker} sent an infinite update: FLTrust has no direction")
         work.keep(kept)
@@ -297,19 +237,4 @@ class FLTrustFedAVGAlgorithm(AggregationAlgorithm):
         out = work.step([c for k, c in enumerate(coef) if k != root_pos], W, v, self.out_dtype)
         work.finish()
         self.last_trust = TrustRecord(list(ids), dropped, kept_ids, self.root_worker, dots, sqnorms, scores, coef, W)
-        return {name: out[i].to(self.out_dtype).view(layout.shapes[i]) for i, name in enumerate(layout.names)}
-
-    def aggregate_worker_data(self) -> Any:
-        parameter = self._aggregate_parameter()
-        other_data: dict[str, Any] = {}
-        # the same message fields as ClippedFedAVGAlgorithm / FedAVGAlgorithm.aggregate_worker_data
-        if self.aggregate_loss:
-            other_data |= FedAVGAlgorithm._FedAVGAlgorithm__aggregate_loss(self._all_worker_data)
-        other_data |= FedAVGAlgorithm._FedAVGAlgorithm__check_and_reduce_other_data(self._all_worker_data)
-        first = next(iter(self._all_worker_data.values()))
-        return wire_class(first, "ParameterMessage")(
-            parameter=parameter,
-            end_training=first.end_training,
-            in_round=first.in_round,
-            other_data=other_data,
-        )
+        return self._named(layout, out)

@@ -27,30 +27,13 @@ restores or dequantises before handing an update over.
 
 from __future__ import annotations
 
-from typing import Any
-
 import torch
 
-from ..fedavg import (
-    ClientTable,
-    ModelLayout,
-    NaNAggregationError,
-    check_robust_rule,
-    out_code,
-    robust_trim,
-)
+from ..fedavg import ClientTable, ModelLayout, NaNAggregationError, check_robust_rule, robust_trim
 from .._native import ROBUST_MAX_CLIENTS
-from ..message import KIND_DELTA, KIND_PARAMETER, Message, ModelParameter, message_kind, wire_class
-from ..quantized import QuantizedTensor
-from .aggregation_algorithm import (
-    AggregationAlgorithm,
-    context_for,
-    default_device,
-    split_empty,
-    to_device_operand,
-    unify_dtype,
-)
-from .fed_avg_algorithm import FedAVGAlgorithm
+from ..message import ModelParameter
+from .aggregation_algorithm import context_for, fill_empty, split_empty, to_device_operand, unify_dtype
+from .dense_round import DenseRoundAlgorithm
 
 _MAGNITUDE = 0x7FFFFFFFFFFFFFFF
 
@@ -83,47 +66,22 @@ def robust_reduce_cpu(tensors: list[torch.Tensor], mode: str, trim: float) -> to
     return out
 
 
-class RobustFedAVGAlgorithm(AggregationAlgorithm):
+class RobustFedAVGAlgorithm(DenseRoundAlgorithm):
     """``mode`` is ``"trimmed_mean"`` (``trim`` in [0, 0.5)) or ``"median"``; ``out_dtype`` float64
     (what the reference's algorithms return) or float32 (that result rounded to nearest even);
     ``device`` a GPU (default: the current one) or the CPU."""
 
-    accepts_delta_messages = False
-    accepts_quantized_messages = False
+    # Of the dense base this rule takes the guard, the device and the result message only. It does not
+    # compare whole updates: ``_columns`` stands in for ``_rows`` (so there is no ``rule_name``), and
+    # ``_alphas`` and ``_previous`` have no meaning here (both rules are unweighted, with no centre).
+    rule_subject = "robust aggregation"
 
     def __init__(self, mode: str = "trimmed_mean", trim: float = 0.1,
                  device: torch.device | str | None = None, out_dtype: torch.dtype = torch.float64) -> None:
-        super().__init__()
         check_robust_rule(mode, trim)
-        out_code(out_dtype)  # TypeError for anything but float32 / float64
+        super().__init__(device, out_dtype)
         self.mode = mode
         self.trim = float(trim)
-        self.out_dtype = out_dtype
-        self.aggregate_loss: bool = False
-        self.__device = torch.device(device) if device is not None else None
-
-    @property
-    def device(self) -> torch.device:
-        if self.__device is None:
-            self.__device = default_device()
-        if self.__device.type == "cuda" and self.__device.index is None:
-            self.__device = torch.device("cuda", torch.cuda.current_device())
-        return self.__device
-
-    def process_worker_data(self, worker_id: int, worker_data: Message | None) -> bool:
-        if worker_data is not None:
-            kind = message_kind(worker_data)
-            if kind == KIND_DELTA:
-                raise NotImplementedError(
-                    "robust aggregation needs full updates: restore a DeltaParameterMessage first "
-                    "(accepts_delta_messages is False, so this package's server does)")
-            if kind != KIND_PARAMETER:
-                raise TypeError(f"robust aggregation takes ParameterMessage updates, not {type(worker_data).__name__}")
-            if any(isinstance(t, QuantizedTensor) for t in worker_data.parameter.values()):
-                raise NotImplementedError(
-                    "robust aggregation reads dense tensors: dequantise QSGD / NNADQ payloads first "
-                    "(accepts_quantized_messages is False, so this package's server does)")
-        return super().process_worker_data(worker_id, worker_data)
 
     # ---- end of round ---------------------------------------------------------------------
     def _columns(self) -> tuple[ModelLayout, dict[str, list[tuple[int, torch.Tensor]]]]:
@@ -174,22 +132,4 @@ class RobustFedAVGAlgorithm(AggregationAlgorithm):
             ctx.raise_on_nan([(table, dt)])
             for j, i in enumerate(keep):
                 result[layout.names[i]] = outs[j].view(layout.shapes[i])
-        for i, name in enumerate(layout.names):
-            if name not in result:
-                result[name] = torch.empty(layout.shapes[i], dtype=self.out_dtype, device=device)
-        return {name: result[name] for name in layout.names}
-
-    def aggregate_worker_data(self) -> Any:
-        parameter = self._aggregate_parameter()
-        other_data: dict[str, Any] = {}
-        # the same message fields as FedAVGAlgorithm.aggregate_worker_data, by its own helpers
-        if self.aggregate_loss:
-            other_data |= FedAVGAlgorithm._FedAVGAlgorithm__aggregate_loss(self._all_worker_data)
-        other_data |= FedAVGAlgorithm._FedAVGAlgorithm__check_and_reduce_other_data(self._all_worker_data)
-        first = next(iter(self._all_worker_data.values()))
-        return wire_class(first, "ParameterMessage")(
-            parameter=parameter,
-            end_training=first.end_training,
-            in_round=first.in_round,
-            other_data=other_data,
-        )
+        return fill_empty(layout, result, self.out_dtype, device)

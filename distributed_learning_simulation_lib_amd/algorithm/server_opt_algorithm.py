@@ -9,12 +9,12 @@ owns. The contract (``tests/opt_reference.py`` restates it indep
 
 1. The ``n`` clients of the round that were not skipped (``None``) count, in arrival order; every
    one of them must hold every tensor of the layout with the same shape (the ``ValueError`` of
-   ``ClippedFedAVGAlgorithm`` names the client and the key). ``c_i`` is the client's
+   ``DenseRoundAlgorithm._rows`` names the client and the key). ``c_i`` is the client's
    ``aggregation_weight`` or, with ``weighted=False``, 1.0. ``W = sum_i c_i``, added in arrival order;
    ``W = 0`` is a ``ValueError``. At most 1024 clients.
 2. ``z`` is the model given to ``set_old_parameter``, converted to float64 and moved to the device
    once per round (never set, or its keys or shapes differ from the layout: the ``ValueError`` of
-   ``ClippedFedAVGAlgorithm`` names the key).
+   ``DenseRoundAlgorithm._previous`` names the key).
 3. Per element, every value converted exactly to float64 and every line one separately rounded
    float64 operation (no FMA, no reciprocal, a correctly rounded square root, no bias correction):
    ``d_i = x_i - z``, ``p_i = c_i * d_i``, ``acc = p_0 + p_1 + ...`` in arrival order,
@@ -58,13 +58,11 @@ from ..fedavg import (
     ModelLayout,
     NaNAggregationError,
     check_server_opt,
-    out_code,
     server_opt_update,
 )
-from ..message import KIND_DELTA, KIND_PARAMETER, Message, ModelParameter, message_kind
-from ..quantized import QuantizedTensor
-from .aggregation_algorithm import AggregationAlgorithm, default_device
-from .clipped_aggregation_algorithm import ClippedFedAVGAlgorithm, _CpuClipRound, _GpuClipRound
+from .._native import POINT_MAX_CLIENTS
+from ..message import ModelParameter
+from .dense_round import DenseRoundAlgorithm, _CpuRound, _GpuRound
 
 
 class ServerOptStep(NamedTuple):
@@ -77,7 +75,7 @@ class ServerOptStep(NamedTuple):
     mode: str
 
 
-class _CpuOptRound(_CpuClipRound):
+class _CpuOptRound(_CpuRound):
     def opt_step(self, coef: list[float], divisor: float, point: list[torch.Tensor], m: list[torch.Tensor],
                  v: list[torch.Tensor] | None, m_out: list[torch.Tensor], v_out: list[torch.Tensor] | None,
                  out_dtype: torch.dtype, mode: str, hyper: tuple[float, ...]) -> list[torch.Tensor]:
@@ -108,23 +106,23 @@ class _CpuOptRound(_CpuClipRound):
         return outs
 
 
-class _GpuOptRound(_GpuClipRound):
+class _GpuOptRound(_GpuRound):
     def opt_step(self, coef: list[float], divisor: float, point: list[torch.Tensor], m: list[torch.Tensor],
                  v: list[torch.Tensor] | None, m_out: list[torch.Tensor], v_out: list[torch.Tensor] | None,
                  out_dtype: torch.dtype, mode: str, hyper: tuple[float, ...]) -> list[torch.Tensor]:
-        outs = [torch.empty(s, dtype=out_dtype, device=self.device) for s in self.layout.shapes]
+        outs, flat_outs = self._outputs(out_dtype)
         if self.native is not None:
             def flat(ts: list[torch.Tensor] | None) -> list[torch.Tensor] | None:
-                return None if ts is None else [ts[i].reshape(-1) for i in self.segments]
+                return None if ts is None else self._flat(ts)
 
             lr, beta1, _, beta2, _, tau = hyper
             self.ctx.server_opt_step(self.table, self.dt, coef, divisor, flat(point), flat(m), flat(v), flat(m_out),
-                                     flat(v_out), [outs[i].view(-1) for i in self.segments], out_dtype,
-                                     mode=mode, lr=lr, beta1=beta1, beta2=beta2, tau=tau)
+                                     flat(v_out), flat_outs, out_dtype, mode=mode, lr=lr, beta1=beta1, beta2=beta2,
+                                     tau=tau)
         return outs
 
 
-class ServerOptFedAVGAlgorithm(AggregationAlgorithm):
+class ServerOptFedAVGAlgorithm(DenseRoundAlgorithm):
     """``optimizer`` is ``"avgm"``, ``"adagrad"``, ``"yogi"`` or ``"adam"``; ``learning_rate`` the
     server's step size (``None``: 1.0 for ``"avgm"``; the adaptive optimisers have no default);
     ``beta1``, ``beta2`` in [0, 1); ``tau`` the adaptivity (finite, > 0); ``initial_second_moment`` the
@@ -132,13 +130,14 @@ class ServerOptFedAVGAlgorithm(AggregationAlgorithm):
     ``aggregation_weight`` instead of 1.0 each; ``out_dtype`` float64 or float32 (that result rounded
     to nearest even); ``device`` a GPU (default: the current one) or the CPU."""
 
-    accepts_delta_messages = False
-    accepts_quantized_messages = False
+    rule_subject = "The server optimisers"
+    rule_verb_ending = ""
+    rule_name = "centred clipping"  # the row checks, the client limit and their texts are centred clipping's
+    max_clients = POINT_MAX_CLIENTS
 
     def __init__(self, optimizer: str, learning_rate: float | None = None, beta1: float = 0.9, beta2: float = 0.99,
                  tau: float = 1e-3, initial_second_moment: float | None = None, weighted: bool = True,
                  device: torch.device | str | None = None, out_dtype: torch.dtype = torch.float64) -> None:
-        super().__init__()
         if optimizer not in SERVER_OPT_MODES:
             raise ValueError(f"optimizer must be one of {SERVER_OPT_MODES}, not {optimizer!r}")
         if learning_rate is None:
@@ -152,48 +151,22 @@ class ServerOptFedAVGAlgorithm(AggregationAlgorithm):
         v0 = float(initial_second_moment)
         if not (v0 >= 0 and math.isfinite(v0)):
             raise ValueError(f"initial_second_moment must be a finite number >= 0, not {initial_second_moment}")
-        out_code(out_dtype)  # TypeError for anything but float32 / float64
+        super().__init__(device, out_dtype)
         self.optimizer = optimizer
         self.learning_rate, self.beta1, self.beta2, self.tau = lr, b1, b2, tau_
         self._hyper = (lr, b1, omb1, b2, omb2, tau_)
         self.initial_second_moment = v0
         self.weighted = bool(weighted)
-        self.out_dtype = out_dtype
-        self.aggregate_loss: bool = False
         self.last_step: ServerOptStep | None = None
         self.rounds_done = 0
         self._layout: ModelLayout | None = None  # the state's layout; None: no state yet
         self._m: list[torch.Tensor] | None = None
         self._v: list[torch.Tensor] | None = None
         self._spare: tuple[list[torch.Tensor], list[torch.Tensor] | None] | None = None
-        self.__device = torch.device(device) if device is not None else None
-
-    @property
-    def device(self) -> torch.device:
-        if self.__device is None:
-            self.__device = default_device()
-        if self.__device.type == "cuda" and self.__device.index is None:
-            self.__device = torch.device("cuda", torch.cuda.current_device())
-        return self.__device
 
     @property
     def adaptive(self) -> bool:
         return self.optimizer != "avgm"
-
-    def process_worker_data(self, worker_id: int, worker_data: Message | None) -> bool:
-        if worker_data is not None:
-            kind = message_kind(worker_data)
-            if kind == KIND_DELTA:
-                raise NotImplementedError(
-                    "The server optimisers need full updates: restore a DeltaParameterMessage first "
-                    "(accepts_delta_messages is False, so this package's server does)")
-            if kind != KIND_PARAMETER:
-                raise TypeError(f"The server optimisers take ParameterMessage updates, not {type(worker_data).__name__}")
-            if any(isinstance(t, QuantizedTensor) for t in worker_data.parameter.values()):
-                raise NotImplementedError(
-                    "The server optimisers read dense tensors: dequantise QSGD / NNADQ payloads first "
-                    "(accepts_quantized_messages is False, so this package's server does)")
-        return super().process_worker_data(worker_id, worker_data)
 
     # ---- the state ------------------------------------------------------------------------
     def reset_state(self) -> None:
@@ -282,17 +255,15 @@ class ServerOptFedAVGAlgorithm(AggregationAlgorithm):
 
     # ---- end of round ---------------------------------------------------------------------
     def _aggregate_parameter(self) -> ModelParameter:
-        # the shape and key checks, the client limit, the weights and the previous model are centred
-        # clipping's (clipped_aggregation_algorithm.py)
-        layout, ids, rows = ClippedFedAVGAlgorithm._rows(self)  # type: ignore[arg-type]
-        coef = ClippedFedAVGAlgorithm._alphas(self, ids)  # type: ignore[arg-type]
+        layout, ids, rows = self._rows()
+        coef = self._alphas(ids)
         W = 0.0
         for c in coef:
             W = W + c
         if not W > 0:
             raise ValueError("the clients' weights add up to 0: the pseudo-gradient is undefined")
         device = self.device
-        previous = ClippedFedAVGAlgorithm._previous(self, layout, device)  # type: ignore[arg-type]
+        previous = self._previous(layout, device)
         m, v, spare_m, spare_v = self._state_for(layout, device)
         work = (_GpuOptRound if device.type == "cuda" else _CpuOptRound)(layout, rows, device)
         out = work.opt_step(coef, W, work.centre(previous), m, v, spare_m, spare_v, self.out_dtype, self.optimizer,
@@ -301,8 +272,4 @@ class ServerOptFedAVGAlgorithm(AggregationAlgorithm):
         self._layout, self._m, self._v, self._spare = layout, spare_m, spare_v, (m, v)
         self.rounds_done += 1
         self.last_step = ServerOptStep(list(ids), coef, W, self.optimizer)
-        return {name: out[i].to(self.out_dtype).view(layout.shapes[i]) for i, name in enumerate(layout.names)}
-
-    def aggregate_worker_data(self) -> Any:
-        # the message assembly of ClippedFedAVGAlgorithm / FedAVGAlgorithm.aggregate_worker_data
-        return ClippedFedAVGAlgorithm.aggregate_worker_data(self)  # type: ignore[arg-type]
+        return self._named(layout, out)

@@ -36,16 +36,16 @@ clients, one GPU; full ``ParameterMessage`` updates are ``FedAVGAlgorithm``'s.
 
 from __future__ import annotations
 
-from typing import Any, NamedTuple
+from typing import NamedTuple
 
 import torch
 
-from ..fedavg import SPARSE_INDEX_MESSAGE, ModelLayout, NaNAggregationError, out_code
+from ..fedavg import SPARSE_INDEX_MESSAGE, ModelLayout, NaNAggregationError
 from .._native import POINT_MAX_CLIENTS
-from ..message import KIND_DELTA, KIND_PARAMETER, Message, ModelParameter, message_kind, wire_class
+from ..message import KIND_DELTA, KIND_PARAMETER, Message, ModelParameter, message_kind
 from ..sparse import VALUE_DTYPES, SparseDelta
-from .aggregation_algorithm import AggregationAlgorithm, context_for, default_device, split_empty
-from .fed_avg_algorithm import FedAVGAlgorithm
+from .aggregation_algorithm import context_for, fill_empty, split_empty
+from .dense_round import RoundAlgorithm
 
 
 class SparseRound(NamedTuple):
@@ -90,7 +90,7 @@ def fold_cpu(rows: list[list[SparseDelta]], weights: list[float], divisor: float
     return outs
 
 
-class SparseFedAVGAlgorithm(AggregationAlgorithm):
+class SparseFedAVGAlgorithm(RoundAlgorithm):
     """``out_dtype`` float64 or float32 (that result rounded to nearest even); ``device`` a GPU
     (default: the current one) or the CPU."""
 
@@ -99,20 +99,8 @@ class SparseFedAVGAlgorithm(AggregationAlgorithm):
     accepts_quantized_messages = False
 
     def __init__(self, device: torch.device | str | None = None, out_dtype: torch.dtype = torch.float64) -> None:
-        super().__init__()
-        out_code(out_dtype)  # TypeError for anything but float32 / float64
-        self.out_dtype = out_dtype
-        self.aggregate_loss: bool = False
+        super().__init__(device, out_dtype)
         self.last_round: SparseRound | None = None
-        self.__device = torch.device(device) if device is not None else None
-
-    @property
-    def device(self) -> torch.device:
-        if self.__device is None:
-            self.__device = default_device()
-        if self.__device.type == "cuda" and self.__device.index is None:
-            self.__device = torch.device("cuda", torch.cuda.current_device())
-        return self.__device
 
     def process_worker_data(self, worker_id: int, worker_data: Message | None) -> bool:
         if worker_data is not None:
@@ -126,7 +114,7 @@ class SparseFedAVGAlgorithm(AggregationAlgorithm):
         return super().process_worker_data(worker_id, worker_data)
 
     # ---- end of round ---------------------------------------------------------------------
-    def _previous(self) -> tuple[ModelLayout, list[torch.Tensor]]:
+    def _base_model(self) -> tuple[ModelLayout, list[torch.Tensor]]:
         old = self._old_parameter
         if not old:
             first = next(iter(next(iter(self._all_worker_data.values())).delta_parameter), "?")
@@ -134,7 +122,7 @@ class SparseFedAVGAlgorithm(AggregationAlgorithm):
                              f"(tensor {first})")
         return ModelLayout.from_parameters(old), list(old.values())
 
-    def _rows(self, layout: ModelLayout, device: torch.device) -> tuple[list[int], list[list[SparseDelta]]]:
+    def _deltas(self, layout: ModelLayout, device: torch.device) -> tuple[list[int], list[list[SparseDelta]]]:
         """The worker ids in arrival order and, per worker, its sparse deltas in layout order on
         ``device``; ValueError for a key that is missing, unknown, of another shape or dtype."""
         ids, rows = [], []
@@ -173,9 +161,9 @@ class SparseFedAVGAlgorithm(AggregationAlgorithm):
 
     def _aggregate_parameter(self) -> ModelParameter:
         assert self._all_worker_data
-        layout, previous = self._previous()
+        layout, previous = self._base_model()
         device = self.device
-        ids, rows = self._rows(layout, device)
+        ids, rows = self._deltas(layout, device)
         ws = [self._all_worker_data[w].aggregation_weight for w in ids]
         assert all(w is not None and w >= 0 for w in ws)
         W = ws[0]
@@ -205,23 +193,5 @@ class SparseFedAVGAlgorithm(AggregationAlgorithm):
                 outs = fold_cpu(kept_rows, weights, divisor, base, self.out_dtype)
             for j, i in enumerate(keep):
                 result[layout.names[i]] = outs[j].view(layout.shapes[i])
-        for i, name in enumerate(layout.names):
-            if name not in result:
-                result[name] = torch.empty(layout.shapes[i], dtype=self.out_dtype, device=device)
         self.last_round = SparseRound(list(ids), [[d.nnz for d in row] for row in rows])
-        return {name: result[name] for name in layout.names}
-
-    def aggregate_worker_data(self) -> Any:
-        parameter = self._aggregate_parameter()
-        other_data: dict[str, Any] = {}
-        # the same message fields as ClippedFedAVGAlgorithm / FedAVGAlgorithm.aggregate_worker_data
-        if self.aggregate_loss:
-            other_data |= FedAVGAlgorithm._FedAVGAlgorithm__aggregate_loss(self._all_worker_data)
-        other_data |= FedAVGAlgorithm._FedAVGAlgorithm__check_and_reduce_other_data(self._all_worker_data)
-        first = next(iter(self._all_worker_data.values()))
-        return wire_class(first, "ParameterMessage")(
-            parameter=parameter,
-            end_training=first.end_training,
-            in_round=first.in_round,
-            other_data=other_data,
-        )
+        return fill_empty(layout, result, self.out_dtype, device)
