@@ -45,12 +45,20 @@ from .message import (
     ParameterMessageBase,
     get_message_size,
 )
-from .quantized import BroadcastQuantizer, philox_uniforms
+from .quantized import (
+    BroadcastDequantizer,
+    BroadcastQuantizer,
+    NNADQClientEndpoint,
+    QuantClientEndpoint,
+    StochasticQuantClientEndpoint,
+    philox_uniforms,
+)
 from .sparse import SparseDelta, TopKErrorFeedback, TopKSparseEndpoint, topk_sparsify, topk_sparsify_parameter
 
 __all__ = [
     "AggregationAlgorithm",
     "AlgorithmRepository",
+    "BroadcastDequantizer",
     "BroadcastQuantizer",
     "BulyanFedAVGAlgorithm",
     "ClientTable",
@@ -72,14 +80,17 @@ __all__ = [
     "ModelLayout",
     "ModelParameter",
     "MultipleWorkerMessage",
+    "NNADQClientEndpoint",
     "NaNAggregationError",
     "ParameterMessage",
     "ParameterMessageBase",
     "PersonalizedFedAVGAlgorithm",
+    "QuantClientEndpoint",
     "RobustFedAVGAlgorithm",
     "ServerOptFedAVGAlgorithm",
     "SparseDelta",
     "SparseFedAVGAlgorithm",
+    "StochasticQuantClientEndpoint",
     "TopKErrorFeedback",
     "TopKSparseEndpoint",
     "add_dp_noise",
@@ -227,6 +238,20 @@ def _register_builtin() -> None:
             client_endpoint_cls=TopKSparseEndpoint,
             algorithm_cls=SparseFedAVGAlgorithm,
         )
+    # FedAvg whose workers send their updates, and receive the broadcast, as QSGD or NNADQ records: the
+    # plain server and rule (which folds records as they are) behind the quantised client endpoints. The
+    # NNADQ weight has no default: the caller binds it through the endpoint's keyword arguments
+    for name, endpoint_cls in (("fed_avg_qsgd", StochasticQuantClientEndpoint), ("fed_avg_nnadq", NNADQClientEndpoint)):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                client_endpoint_cls=endpoint_cls,
+                algorithm_cls=FedAVGAlgorithm,
+            )
 
 
 _register_builtin()

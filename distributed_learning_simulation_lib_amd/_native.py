@@ -146,6 +146,8 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_quant_encode": (
         c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_double,
                   ctypes.c_uint64, c_uint32, c_void_p]),
+    # the record decoder (quant_kernels.hip); tables as raw addresses
+    "fedavg_quant_decode": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     # the clip-and-noise pass of the differential-privacy endpoints (dp_kernels.hip); tables as raw addresses
     "fedavg_dp_noise": (
         c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_double, c_double,

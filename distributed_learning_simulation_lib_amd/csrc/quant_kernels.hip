@@ -28,6 +28,21 @@
 //     the sign area is written as zeros by the lanes whose 16 elements reach past the tensor's end.
 //     The inputs are read by 16-byte loads where the lane's 16 elements are complete and so aligned,
 //     else element by element.
+//
+// The record decoder (fedavg_quant_decode) is the way back: the `get` half of the
+// reference's QuantClientEndpoint (quantized_endpoint.py:32-39) and the dequantisation of
+// QuantServerEndpoint.get (:69-77) for consumers of dense tensors. One launch over the same tiles:
+//   QSGD:  a = norm * sign;  b = a * slot;  x = b / level        NNADQ: t = code * step;  x = t + lo
+// each line one rounding in F, the formulas of oracle/qsgd_oracle.py:dequantize and
+// oracle/nnadq_oracle.py:dequantize and of the fold's in-kernel dequantisation, for every byte pattern.
+//   * quant_decode_kernel: a lane owns the same 16 consecutive elements: one 16-byte load of slots or
+//     codes and one 2-byte load of sign bits (both aligned, both inside the record's padded areas),
+//     the header read by every workgroup for itself (wave-uniform loads). The outputs are aligned to
+//     their element only: a complete lane stores single elements up to the first 16-byte boundary,
+//     16-byte vectors from there and single elements after the last boundary; an incomplete lane (a
+//     tensor's end) stores element by element. An fp32 codec can write the exact fp64 widening of the
+//     same values to a second output in the same pass. A header whose level lies outside [1, 255] and
+//     a decoded element that is not finite raise the context's input flag.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -384,6 +399,144 @@ __global__ __launch_bounds__(kQThreads) void quant_encode_kernel(QArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// the decoder: blockIdx.x = tile
+// ---------------------------------------------------------------------------------------
+struct DArgs {
+  const Span* tiles;
+  const uint8_t* const* rec;  // [T], 16-byte aligned; NULL only where numel == 0
+  void* const* out;           // [T], dtype F, aligned to the element
+  void* const* out64;         // [T] fp64 (the WIDE kernels), else unused
+  const int64_t* numel;       // [T]
+  uint32_t* flag;             // the context's NaN words (0 acc, 1 result, 2 input)
+};
+
+template <typename F>
+struct QVec;
+template <>
+struct QVec<float> {
+  using T = f32x4;
+};
+template <>
+struct QVec<double> {
+  using T = f64x2;
+};
+
+// A complete lane's 16 values with H single elements before the first 16-byte boundary of dst:
+// 16-byte stores from there, single elements after the last boundary.
+template <typename F, int H>
+__device__ __forceinline__ void q_store_peeled(F* dst, const F* x) {
+  using V = typename QVec<F>::T;
+  constexpr int N = 16 / static_cast<int>(sizeof(F));
+  F FEDAVG_AS_GLOBAL* p = (F FEDAVG_AS_GLOBAL*)dst;
+#pragma unroll
+  for (int i = 0; i < H; ++i) p[i] = x[i];
+  constexpr int kVecs = (kQPerLane - H) / N;
+#pragma unroll
+  for (int j = 0; j < kVecs; ++j) {
+    V v;
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = x[H + j * N + k];
+    *(V FEDAVG_AS_GLOBAL*)(p + H + j * N) = v;
+  }
+#pragma unroll
+  for (int i = H + kVecs * N; i < kQPerLane; ++i) p[i] = x[i];
+}
+
+// the lane's values x[0 .. have) to dst[0 .. have); dst is aligned to the element only
+template <typename F>
+__device__ __forceinline__ void q_store16(F* dst, int have, const F* x) {
+  if (have == kQPerLane) {
+    // elements before the first 16-byte boundary: 0 .. 3 (fp32), 0 .. 1 (fp64)
+    const unsigned h = ((16u - (static_cast<unsigned>(reinterpret_cast<uintptr_t>(dst)) & 15u)) & 15u) /
+                       static_cast<unsigned>(sizeof(F));
+    if (h == 0u) q_store_peeled<F, 0>(dst, x);
+    else if (h == 1u) q_store_peeled<F, 1>(dst, x);
+    else if constexpr (sizeof(F) == 4) {
+      if (h == 2u) q_store_peeled<F, 2>(dst, x);
+      else q_store_peeled<F, 3>(dst, x);
+    }
+  } else {
+    F FEDAVG_AS_GLOBAL* p = (F FEDAVG_AS_GLOBAL*)dst;
+#pragma unroll
+    for (int i = 0; i < kQPerLane; ++i) {
+      if (i < have) p[i] = x[i];
+    }
+  }
+}
+
+template <typename F, bool NNADQ, bool WIDE>
+__global__ __launch_bounds__(kQThreads) void quant_decode_kernel(DArgs a) {
+  const int t = static_cast<int>(threadIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
+  const int32_t seg = tp->seg;
+  const int32_t count = tp->count;
+  const int64_t start = tp->start;
+  const uint8_t* const rec = a.rec[seg];
+  const int64_t e0 = start + static_cast<int64_t>(t) * kQPerLane;  // the lane's first element in the tensor
+  const int left = count - t * kQPerLane;
+  const int have = left < 0 ? 0 : (left > kQPerLane ? kQPerLane : left);
+
+  F x[kQPerLane];
+#pragma unroll
+  for (int i = 0; i < kQPerLane; ++i) x[i] = static_cast<F>(0);
+  bool bad;
+  // e0 < numel where have > 0, and e0 is a multiple of 16: the lane's 16 bytes lie inside the slot /
+  // code area (numel rounded up to 16), its 2 sign bytes inside the sign area (likewise)
+  if (!NNADQ) {
+    const ulonglong2 h = *reinterpret_cast<const ulonglong2*>(rec);
+    const F norm = static_cast<F>(__longlong_as_double(static_cast<long long>(h.x)));
+    const int32_t ilevel = static_cast<int32_t>(static_cast<uint32_t>(h.y));
+    const F level = static_cast<F>(ilevel);
+    bad = ilevel < 1 || ilevel > 255;
+    if (have > 0) {
+      const int64_t n = a.numel[seg];
+      const int64_t area = (n + 15) & ~static_cast<int64_t>(15);
+      const u32x4 c = *(const u32x4 FEDAVG_AS_GLOBAL*)(rec + 16 + e0);
+      const uint32_t sw = *(const uint16_t FEDAVG_AS_GLOBAL*)(rec + 16 + area + (e0 >> 3));
+#pragma unroll
+      for (int i = 0; i < kQPerLane; ++i) {
+        const uint32_t slot = (c[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        // numpy.packbits: element i of a byte's eight is bit 7 - i; byte 1 follows byte 0
+        const bool plus = ((sw >> ((i & 8) + 7 - (i & 7))) & 1u) != 0u;
+        const F sign = plus ? static_cast<F>(1) : static_cast<F>(-1);
+        const F ns = norm * sign;
+        const F p = ns * static_cast<F>(slot);
+        x[i] = p / level;
+      }
+    }
+  } else {
+    const ulonglong2 h0 = *reinterpret_cast<const ulonglong2*>(rec);
+    const unsigned long long h1 = *reinterpret_cast<const unsigned long long*>(rec + 16);
+    const F lo = static_cast<F>(__longlong_as_double(static_cast<long long>(h0.x)));
+    const F step = static_cast<F>(__longlong_as_double(static_cast<long long>(h0.y)));
+    const int32_t levels = static_cast<int32_t>(static_cast<uint32_t>(h1));
+    bad = levels < 1 || levels > 255;
+    if (have > 0) {
+      const u32x4 c = *(const u32x4 FEDAVG_AS_GLOBAL*)(rec + 32 + e0);
+#pragma unroll
+      for (int i = 0; i < kQPerLane; ++i) {
+        const uint32_t code = (c[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        const F p = static_cast<F>(code) * step;
+        x[i] = p + lo;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kQPerLane; ++i) bad |= i < have && (QT<F>::bits(x[i]) & QT<F>::kExp) == QT<F>::kExp;
+
+  if (have > 0) {
+    q_store16<F>(static_cast<F*>(a.out[seg]) + e0, have, x);
+    if (WIDE) {
+      double w[kQPerLane];
+#pragma unroll
+      for (int i = 0; i < kQPerLane; ++i) w[i] = static_cast<double>(x[i]);  // exact
+      q_store16<double>(static_cast<double*>(a.out64[seg]) + e0, have, w);
+    }
+  }
+  if (__ballot(bad) != 0ull && (t & 63) == 0) raise_flag(a.flag, 2);
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 struct QuantState {
@@ -411,6 +564,20 @@ int32_t ensure_state(void** slot, QuantState** out) {
 }
 
 size_t align16(size_t n) { return (n + 15) & ~static_cast<size_t>(15); }
+
+// The tile table: tensor by tensor, tiles of kQTile elements (a tensor's last tile is shorter);
+// first[t] (where asked for) is tensor t's first tile, first[T] the number of tiles.
+void cut_tiles(const int64_t* numels, int T, Span* tiles, int32_t* first) {
+  size_t k = 0;
+  for (int t = 0; t < T; ++t) {
+    if (first) first[t] = static_cast<int32_t>(k);
+    for (int64_t b = 0; b < numels[t]; b += kQTile) {
+      const int64_t left = numels[t] - b;
+      tiles[k++] = Span{t, static_cast<int32_t>(left < kQTile ? left : kQTile), b};
+    }
+  }
+  if (first) first[T] = static_cast<int32_t>(k);
+}
 
 template <typename F>
 void launch_all(bool nnadq, unsigned tiles, unsigned tensors, hipStream_t s, const QArgs& a) {
@@ -510,16 +677,8 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
   Span* const h_tiles = reinterpret_cast<Span*>(sl.host);
   int32_t* const h_first = reinterpret_cast<int32_t*>(sl.host + o_first);
   uint32_t* const h_ids = reinterpret_cast<uint32_t*>(sl.host + o_id);
-  size_t k = 0;
-  for (int t = 0; t < T; ++t) {
-    h_first[t] = static_cast<int32_t>(k);
-    h_ids[t] = tensor_ids ? tensor_ids[t] : static_cast<uint32_t>(t);
-    for (int64_t b = 0; b < numels[t]; b += kQTile) {
-      const int64_t left = numels[t] - b;
-      h_tiles[k++] = Span{t, static_cast<int32_t>(left < kQTile ? left : kQTile), b};
-    }
-  }
-  h_first[T] = static_cast<int32_t>(k);
+  for (int t = 0; t < T; ++t) h_ids[t] = tensor_ids ? tensor_ids[t] : static_cast<uint32_t>(t);
+  cut_tiles(numels, T, h_tiles, h_first);
   std::memcpy(sl.host + o_in, in_ptrs, sizeof(void*) * static_cast<size_t>(T));
   std::memcpy(sl.host + o_rec, record_ptrs, sizeof(void*) * static_cast<size_t>(T));
   std::memcpy(sl.host + o_numel, numels, sizeof(int64_t) * static_cast<size_t>(T));
@@ -546,5 +705,97 @@ extern "C" int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const voi
   if (e == hipSuccess) e = er;
   if (e != hipSuccess)
     return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("quant encode launch: ") + hipGetErrorString(e)).c_str());
+  return FEDAVG_OK;
+}
+
+extern "C" int32_t fedavg_quant_decode(fedavg_ctx* ctx, int32_t codec, const void* const* record_ptrs,
+                                       const int64_t* numels, int32_t num_tensors, void* const* out_ptrs,
+                                       void* const* out64_ptrs, void* stream) {
+  fedavg_robust_view v;
+  const int32_t rv = fedavg_internal_robust_view(ctx, &v);
+  if (rv != FEDAVG_OK) return rv;
+  void** slot = nullptr;
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_QUANT, &slot);
+  if (rs != FEDAVG_OK) return rs;
+  if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
+  if (codec != FEDAVG_QSGD_F32 && codec != FEDAVG_QSGD_F64 && codec != FEDAVG_NNADQ_F32 && codec != FEDAVG_NNADQ_F64)
+    return invalid("the decoder reads QSGD or NNADQ records of fp32 or fp64 tensors");
+  const bool nnadq = codec == FEDAVG_NNADQ_F32 || codec == FEDAVG_NNADQ_F64;
+  const bool f64 = codec == FEDAVG_QSGD_F64 || codec == FEDAVG_NNADQ_F64;
+  const bool wide = out64_ptrs != nullptr;
+  if (record_ptrs == nullptr || numels == nullptr || out_ptrs == nullptr)
+    return invalid("null record table, element counts or output table");
+  if (wide && f64) return invalid("the fp64 copy is offered for the fp32 codecs: an fp64 codec's output is fp64");
+  if (num_tensors < 1 || num_tensors > kQMaxTensors)
+    return invalid("the decoder takes between 1 and " + std::to_string(kQMaxTensors) + " tensors");
+  const int T = num_tensors;
+  const uintptr_t elem = f64 ? 8u : 4u;
+  uint64_t num_tiles = 0;
+  for (int t = 0; t < T; ++t) {
+    if (numels[t] < 0) return invalid("tensor " + std::to_string(t) + ": negative element count");
+    if (numels[t] > 0 && record_ptrs[t] == nullptr) return invalid("tensor " + std::to_string(t) + ": null record");
+    if (misaligned(record_ptrs[t], 16))
+      return invalid("tensor " + std::to_string(t) + ": record not aligned to 16 bytes");
+    if (numels[t] > 0 && out_ptrs[t] == nullptr) return invalid("tensor " + std::to_string(t) + ": null output");
+    if (misaligned(out_ptrs[t], elem))
+      return invalid("tensor " + std::to_string(t) + ": output not aligned to its element size");
+    if (wide) {
+      if (numels[t] > 0 && out64_ptrs[t] == nullptr)
+        return invalid("tensor " + std::to_string(t) + ": null fp64 output");
+      if (misaligned(out64_ptrs[t], 8))
+        return invalid("tensor " + std::to_string(t) + ": fp64 output not aligned to 8 bytes");
+    }
+    num_tiles += (static_cast<uint64_t>(numels[t]) + kQTile - 1) / kQTile;
+  }
+  if (num_tiles > 0x7fffffffull) return invalid("layout too large for one decode call");
+  if (num_tiles == 0) return FEDAVG_OK;  // nothing but empty tensors: nothing to write
+
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
+  QuantState* st = nullptr;
+  const int32_t re = ensure_state(slot, &st);
+  if (re != FEDAVG_OK) return re;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+
+  // the call's tables: the tiles, [T] record pointers, [T] output pointers, [T] fp64 output pointers
+  // (zeros without them), [T] element counts
+  const size_t tile_bytes = align16(sizeof(Span) * num_tiles);
+  const size_t ptr_bytes = align16(sizeof(void*) * static_cast<size_t>(T));
+  const size_t o_rec = tile_bytes, o_out = o_rec + ptr_bytes, o_out64 = o_out + ptr_bytes,
+               o_numel = o_out64 + ptr_bytes;
+  const size_t bytes = o_numel + ptr_bytes;
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.peek(bytes, &slp));
+  TableRing::Slot& sl = *slp;
+  std::memset(sl.host, 0, bytes);
+  cut_tiles(numels, T, reinterpret_cast<Span*>(sl.host), nullptr);
+  std::memcpy(sl.host + o_rec, record_ptrs, sizeof(void*) * static_cast<size_t>(T));
+  std::memcpy(sl.host + o_out, out_ptrs, sizeof(void*) * static_cast<size_t>(T));
+  if (wide) std::memcpy(sl.host + o_out64, out64_ptrs, sizeof(void*) * static_cast<size_t>(T));
+  std::memcpy(sl.host + o_numel, numels, sizeof(int64_t) * static_cast<size_t>(T));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
+
+  DArgs a;
+  a.tiles = reinterpret_cast<const Span*>(sl.dev);
+  a.rec = reinterpret_cast<const uint8_t* const*>(sl.dev + o_rec);
+  a.out = reinterpret_cast<void* const*>(sl.dev + o_out);
+  a.out64 = reinterpret_cast<void* const*>(sl.dev + o_out64);
+  a.numel = reinterpret_cast<const int64_t*>(sl.dev + o_numel);
+  a.flag = v.d_flag;
+  const dim3 grid(static_cast<unsigned>(num_tiles)), block(kQThreads);
+  if (f64) {
+    if (nnadq) hipLaunchKernelGGL((quant_decode_kernel<double, true, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((quant_decode_kernel<double, false, false>), grid, block, 0, s, a);
+  } else if (wide) {
+    if (nnadq) hipLaunchKernelGGL((quant_decode_kernel<float, true, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((quant_decode_kernel<float, false, true>), grid, block, 0, s, a);
+  } else {
+    if (nnadq) hipLaunchKernelGGL((quant_decode_kernel<float, true, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((quant_decode_kernel<float, false, false>), grid, block, 0, s, a);
+  }
+  hipError_t e = hipGetLastError();
+  const hipError_t er = st->ring.commit(sl, s);
+  if (e == hipSuccess) e = er;
+  if (e != hipSuccess)
+    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("quant decode launch: ") + hipGetErrorString(e)).c_str());
   return FEDAVG_OK;
 }

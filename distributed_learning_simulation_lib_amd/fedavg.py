@@ -1203,6 +1203,51 @@ class FedAvgContext:
             )
         )
 
+    def quant_decode(self, codec: int, records: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                     outs64: Sequence[torch.Tensor] | None = None) -> None:
+        """Decode QSGD or NNADQ ``records`` of one codec (16-byte aligned uint8 tensors on the
+        context's device: the context's layout plays no part) into ``outs`` in one launch
+        (``fedavg_quant_decode``). ``codec`` is one of ``_native.QSGD_F32 / QSGD_F64 /
+        NNADQ_F32 / NNADQ_F64`` and names the outputs' dtype; ``outs[t]`` is a contiguous tensor of
+        that dtype, aligned to its element only, whose element count is the record's, and exactly
+        those elements are written. ``outs64`` (fp32 codecs only) are fp64 tensors of the same sizes
+        that receive the exact widening of the same values in the same pass. Asynchronous; a header
+        whose level lies outside [1, 255] or a decoded element that is not finite latches the input
+        flag, which ``raise_on_nan`` turns into ``NaNAggregationError``."""
+        if codec not in _native.RECORD_CODES:
+            raise ValueError(f"codec {codec} is not a record format")
+        f64 = codec in (_native.QSGD_F64, _native.NNADQ_F64)
+        nnadq = codec in (_native.NNADQ_F32, _native.NNADQ_F64)
+        dt = torch.float64 if f64 else torch.float32
+        T = len(records)
+        if T == 0 or len(outs) != T or (outs64 is not None and len(outs64) != T):
+            raise ValueError("one output per record and at least one record are required")
+        if outs64 is not None and f64:
+            raise ValueError("the fp64 copy is offered for the fp32 codecs: an fp64 codec's output is fp64")
+        ptrs = np.zeros((3, T), dtype=np.uint64)  # record, output, fp64 output
+        numels = np.zeros(T, dtype=np.int64)
+        for t, (r, o) in enumerate(zip(records, outs)):
+            if o.dtype != dt or o.device != self.device or not o.is_contiguous():
+                raise ValueError(f"output {t}: a contiguous {dt} tensor on {self.device} is required")
+            n = o.numel()
+            need = 32 + (n + 15) // 16 * 16 if nnadq else 16 + (n + 15) // 16 * 16 + ((n + 7) // 8 + 15) // 16 * 16
+            if r.dtype != torch.uint8 or r.device != self.device or not r.is_contiguous() or r.numel() != need:
+                raise ValueError(f"record {t}: a contiguous uint8 tensor of {need} bytes on {self.device} is required")
+            ptrs[0, t], ptrs[1, t] = r.data_ptr(), o.data_ptr() if n else 0
+            if outs64 is not None:
+                w = outs64[t]
+                if w.dtype != torch.float64 or w.device != self.device or not w.is_contiguous() or w.numel() != n:
+                    raise ValueError(f"fp64 output {t}: a contiguous torch.float64 tensor of {n} elements on "
+                                     f"{self.device} is required")
+                ptrs[2, t] = w.data_ptr() if n else 0
+            numels[t] = n
+        _native.check(
+            self._lib.fedavg_quant_decode(
+                self._h, codec, ptrs[0].ctypes.data, numels.ctypes.data, T, ptrs[1].ctypes.data,
+                ptrs[2].ctypes.data if outs64 is not None else None, self.stream,
+            )
+        )
+
     def dp_noise(self, tensors: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], C: float, noise_scale: float,
                  seed: int = 0, draw: int = 0, tensor_ids: Sequence[int] | None = None, row_len: int = 0) -> None:
         """Clip and noise ``tensors`` (contiguous tensors of one floating dtype on the context's

@@ -26,20 +26,27 @@ unpinned (``oracle/qsgd_oracle.py`` and ``oracle/nnadq_oracle.py`` say what exac
 ``stochastic_quantization`` and ``NNADQ`` below are this framework's client-side quantisers (and
 host dequantisers for consumers that need dense tensors, e.g. workers receiving a quantised
 broadcast); the server-side hot path never calls ``dequantize_tensor``.
+
+The worker's side is at the end of the module: ``BroadcastDequantizer`` and the quantised client
+endpoints, which decode records on a GPU with ``fedavg_quant_decode``, as
+``dequantize_tensor`` and ``dequantize_parameter`` do for records that lie there.
 """
 
 from __future__ import annotations
 
 import logging
 import math
+import os
 from collections.abc import Callable, Mapping
 from dataclasses import dataclass
+from typing import Any
 
 import numpy as np
 import torch
 
 from . import _native
 from .fedavg import FedAvgContext, ModelLayout, NaNAggregationError
+from .message import is_parameter_message
 
 _log = logging.getLogger(__name__)
 
@@ -229,9 +236,18 @@ def quantize_tensor(
 
 
 def dequantize_tensor(q: QuantizedTensor) -> torch.Tensor:
-    """Dense x_hat in the codec's dtype (host-side consumers; the server's FedAvg fold
-    dequantises inside the kernel instead): QSGD ((norm * sign) * slot) / level, NNADQ
-    code * step + lo."""
+    """Dense x_hat in the codec's dtype (consumers of dense tensors; the server's FedAvg fold
+    dequantises inside its kernel instead): QSGD ((norm * sign) * slot) / level, NNADQ
+    code * step + lo. A record on a GPU is decoded there by ``fedavg_quant_decode`` (one launch,
+    DESIGN.md §5u), a host record by torch ops on the host: the same bits either way. Non-finite
+    values are handed on as they come (the consumer's own check sees them)."""
+    if q.record.device.type == "cuda":
+        return _decode_plain({"x": q})["x"]
+    return _dequantize_host(q)
+
+
+def _dequantize_host(q: QuantizedTensor) -> torch.Tensor:
+    """The decoder as eager torch ops, one rounding per op in the codec's dtype."""
     dt = q.codec.value_dtype
     rec = q.record
     if q.codec.scheme == "nnadq":
@@ -268,8 +284,62 @@ def is_quantized(parameter: Mapping[str, object]) -> bool:
 
 def dequantize_parameter(parameter: Mapping[str, object]) -> dict[str, object]:
     """QuantServerEndpoint.get's dequantisation (quantized_endpoint.py:69-77) for consumers
-    that cannot take records (the fused FedAvg path never calls this)."""
-    return {k: dequantize_tensor(v) if isinstance(v, QuantizedTensor) else v for k, v in parameter.items()}
+    that cannot take records (the fused FedAvg path never calls this). Records on a GPU are
+    decoded there, one ``fedavg_quant_decode`` launch per codec present; host records by the host
+    path; dense values pass through."""
+    if any(isinstance(v, QuantizedTensor) and v.record.device.type == "cuda" for v in parameter.values()):
+        return _decode_plain(parameter)
+    return {k: _dequantize_host(v) if isinstance(v, QuantizedTensor) else v for k, v in parameter.items()}
+
+
+# -- the record decoder on the device (fedavg_quant_decode, DESIGN.md §5u) -------------------------
+
+_DecodeItem = tuple[QuantizedTensor, torch.Tensor, torch.Tensor | None]  # record, flat output, flat fp64 output
+
+
+def _decode_on_device(ctx: FedAvgContext, items: list[_DecodeItem]) -> None:
+    """Enqueue the decode of ``(record, flat output, flat fp64 output or None)`` triples that lie on
+    the context's device: one launch per codec present (two where only part of a codec's records
+    carry an fp64 output)."""
+    groups: dict[tuple[int, bool], list[_DecodeItem]] = {}
+    for item in items:
+        if item[0].numel:
+            groups.setdefault((item[0].codec.code, item[2] is not None), []).append(item)
+    for (code, wide), group in sorted(groups.items()):
+        ctx.quant_decode(code, [_aligned_record(q.record) for q, _, _ in group], [o for _, o, _ in group],
+                         [w for _, _, w in group] if wide else None)
+
+
+def _aligned_record(record: torch.Tensor) -> torch.Tensor:
+    """The record as the kernel takes it: contiguous and 16-byte aligned (a copy where it is not)."""
+    record = record.contiguous()
+    return record if record.data_ptr() % 16 == 0 else record.clone()
+
+
+_plain_contexts: dict[torch.device, FedAvgContext] = {}
+
+
+def _decode_plain(parameter: Mapping[str, object]) -> dict[str, object]:
+    """``dequantize_parameter`` with the device records decoded by the kernel into fresh tensors.
+    The context's flag is not read: what the contract's lines give is handed on, finite or not, as
+    the host path hands it on (the kernel writes every element by those lines either way)."""
+    out: dict[str, object] = {}
+    by_device: dict[torch.device, list[_DecodeItem]] = {}
+    for name, v in parameter.items():
+        if not isinstance(v, QuantizedTensor):
+            out[name] = v
+        elif v.record.device.type != "cuda":
+            out[name] = _dequantize_host(v)
+        else:
+            dense = torch.empty(v.shape, dtype=v.codec.value_dtype, device=v.record.device)
+            by_device.setdefault(v.record.device, []).append((v, dense.reshape(-1), None))
+            out[name] = dense
+    for device, items in by_device.items():
+        ctx = _plain_contexts.get(device)
+        if ctx is None:
+            ctx = _plain_contexts[device] = FedAvgContext(ModelLayout.flat(1, "quant"), device)
+        _decode_on_device(ctx, items)
+    return {name: out[name] for name in parameter}
 
 
 def record_layout(numels: list[int], codec: QuantizedDtype = QSGD_F32) -> ModelLayout:
@@ -532,6 +602,11 @@ class BroadcastQuantizer:
             blob = self._blobs[device] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
         return blob
 
+    def detach_blobs(self) -> None:
+        """Forget the device blobs: the records of the calls so far keep theirs alive and stay
+        valid, and the next call on a device starts a new blob."""
+        self._blobs.clear()
+
     def _plan(self, parameter: Mapping[str, torch.Tensor]) -> list[tuple[str, torch.Tensor, QuantizedDtype, int]]:
         plan = []
         for t, (name, value) in enumerate(parameter.items()):
@@ -598,3 +673,265 @@ class BroadcastQuantizer:
             # a record of its own storage: a transport that pickles tensors sends a view's whole storage
             out[name] = QuantizedTensor(host[off : off + q.record.numel()].clone(), q.shape, q.codec)
         return out
+
+
+# -- the worker's side (QuantClientEndpoint, quantized_endpoint.py:17-51, :102-105, :114-124) -------
+#
+# A worker behind a quantised endpoint receives the server's broadcast as records and sends its own
+# update as records. On a GPU the records are decoded by fedavg_quant_decode (csrc/quant_kernels.hip,
+# DESIGN.md §5u) where they lie, or after one upload of about 1.1 bytes per element, straight into
+# the model's own parameters if the worker says so; host records are decoded on the host.
+
+_FLAGGED = "a record's level lies outside [1, 255] or an element decodes to a non-finite value"
+
+
+class BroadcastDequantizer:
+    """The counterpart of ``BroadcastQuantizer``: ``dequantizer(records, device=None, out=None,
+    f64_out=None)`` turns a dict of records into a dict of dense tensors in the codecs' dtypes,
+    what the reference's quantised client endpoints do in ``get`` once ``dequant_server_data()`` was
+    called (quantized_endpoint.py:32-39). Dense values in the dict pass through unchanged.
+
+    Records on a GPU are decoded there by ``fedavg_quant_decode``, one launch per codec present.
+    Host records with ``device=`` a GPU are packed into one pinned blob, cross in one copy (about
+    1.1 bytes per element instead of the 4 or 8 of a dense tensor) and are decoded on that device.
+    Host records without a ``device`` are decoded on the host. The bits are the same in every case.
+
+    ``out`` maps names to existing tensors that are written in place and returned, e.g. the model's
+    own parameters: the codec's dtype, the record's shape, on the device where the record is
+    decoded, contiguous but aligned to the element only; anything else is a ``ValueError``. Names
+    it does not hold get new tensors. ``f64_out`` likewise maps names of fp32 records to fp64
+    tensors that receive the exact widening of the same values in the same pass (what a worker's
+    model cache keeps); naming an fp64 record there is a ``ValueError``.
+
+    A header whose level lies outside [1, 255], or an element that decodes to a non-finite value, is
+    refused with ``NaNAggregationError`` (an ``AssertionError``, ``stage="input"``) and no tensor is
+    handed out; what ``out`` holds then is unspecified. The dequantizer keeps one context and one
+    reusable blob per device."""
+
+    def __init__(self) -> None:
+        self._contexts: dict[torch.device, FedAvgContext] = {}
+        self._blobs: dict[torch.device, torch.Tensor] = {}
+        self._pinned: dict[torch.device, torch.Tensor] = {}
+
+    def _context(self, device: torch.device) -> FedAvgContext:
+        ctx = self._contexts.get(device)
+        if ctx is None:
+            # the decoder does not depend on a context's layout: a one-element layout carries the
+            # device, the stream order, the flag words and the call's workspace
+            ctx = self._contexts[device] = FedAvgContext(ModelLayout.flat(1, "quant"), device)
+        return ctx
+
+    @staticmethod
+    def _given(table: Mapping[str, torch.Tensor] | None, name: str, q: QuantizedTensor, dtype: torch.dtype,
+               device: torch.device, what: str) -> torch.Tensor | None:
+        t = None if table is None else table.get(name)
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            kind = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}[{name!r}]: a {dtype} tensor is required, not {kind}")
+        if tuple(t.shape) != q.shape or t.device != device:
+            raise ValueError(f"{what}[{name!r}]: shape {q.shape} on {device} is required, not {tuple(t.shape)} on "
+                             f"{t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}[{name!r}]: the decoder writes contiguous tensors (any element alignment)")
+        return t
+
+    def _upload(self, device: torch.device,
+                items: list[tuple[str, QuantizedTensor]]) -> list[tuple[str, QuantizedTensor]]:
+        """The host records of ``items`` on ``device``: packed into the pinned blob, one copy."""
+        total = sum(q.record.numel() for _, q in items)  # every record is a multiple of 16 bytes
+        pinned = self._pinned.get(device)
+        if pinned is None or pinned.numel() < total:
+            pinned = self._pinned[device] = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+        blob = self._blobs.get(device)
+        if blob is None or blob.numel() < total:
+            blob = self._blobs[device] = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+        off = 0
+        moved = []
+        for name, q in items:
+            n = q.record.numel()
+            pinned[off : off + n].copy_(q.record)
+            moved.append((name, QuantizedTensor(blob[off : off + n], q.shape, q.codec)))
+            off += n
+        # the pinned blob is free again when this call returns: the flag check waits for the stream
+        blob[:total].copy_(pinned[:total], non_blocking=True)
+        return moved
+
+    def __call__(self, records: Mapping[str, object], device: torch.device | str | None = None,
+                 out: Mapping[str, torch.Tensor] | None = None,
+                 f64_out: Mapping[str, torch.Tensor] | None = None) -> dict[str, object]:
+        target = None if device is None else torch.device(device)
+        if target is not None and target.type == "cuda" and target.index is None:
+            target = torch.device("cuda", torch.cuda.current_device())
+        result: dict[str, object] = {}
+        on_host: list[tuple[str, QuantizedTensor]] = []
+        to_upload: list[tuple[str, QuantizedTensor]] = []
+        on_device: dict[torch.device, list[tuple[str, QuantizedTensor]]] = {}
+        for name, v in records.items():
+            if not isinstance(v, QuantizedTensor):
+                result[name] = v
+            elif v.record.device.type == "cuda":
+                on_device.setdefault(v.record.device, []).append((name, v))
+            elif target is not None and target.type == "cuda":
+                to_upload.append((name, v))
+            else:
+                on_host.append((name, v))
+        # every output is checked before anything is written
+        plan: dict[str, tuple[torch.Tensor | None, torch.Tensor | None]] = {}
+        for where, items in [(torch.device("cpu"), on_host), (target, to_upload), *on_device.items()]:
+            for name, q in items:
+                wide = self._given(f64_out, name, q, torch.float64, where, "f64_out")
+                if wide is not None and q.codec.value_dtype == torch.float64:
+                    raise ValueError(f"f64_out[{name!r}]: the fp64 copy is offered for fp32 records; this one "
+                                     "decodes to fp64")
+                plan[name] = (self._given(out, name, q, q.codec.value_dtype, where, "out"), wide)
+
+        decoded = {name: self._decode_host(name, q) for name, q in on_host}
+        if to_upload:
+            on_device.setdefault(target, []).extend(self._upload(target, to_upload))
+        for where, items in on_device.items():
+            triples = []
+            for name, q in items:
+                dense, wide = plan[name]
+                if dense is None:
+                    dense = torch.empty(q.shape, dtype=q.codec.value_dtype, device=where)
+                result[name] = dense
+                triples.append((q, dense.reshape(-1), None if wide is None else wide.reshape(-1)))
+            ctx = self._context(where)
+            _decode_on_device(ctx, triples)
+            if ctx.flags() & _native.FLAG_INPUT_NAN:  # waits for the stream
+                ctx.reset()  # the flag is sticky until reset: the context stays usable
+                raise NaNAggregationError("input", f"the records on {where}: {_FLAGGED}")
+        for name, dense in decoded.items():
+            given, wide = plan[name]
+            if wide is not None:
+                wide.copy_(dense)  # fp32 -> fp64: exact
+            result[name] = dense if given is None else given.copy_(dense)
+        return {name: result[name] for name in records}
+
+    @staticmethod
+    def _decode_host(name: str, q: QuantizedTensor) -> torch.Tensor:
+        level = q.levels if q.codec.scheme == "nnadq" else q.level
+        dense = _dequantize_host(q)
+        if not 1 <= level <= 255 or not bool(torch.isfinite(dense).all()):
+            raise NaNAggregationError("input", f"{name}: {_FLAGGED}")
+        return dense
+
+
+class QuantClientEndpoint:
+    """Wraps a client endpoint (any object with ``get()`` and ``send(data)``) as the reference's
+    ``QuantClientEndpoint`` does its base class (quantized_endpoint.py:17-51): ``send`` quantises a
+    ``ParameterMessage``'s ``parameter`` with ``quant``, calls ``_after_quant`` and hands it on;
+    ``get`` dequantises a ``ParameterMessage``'s ``parameter`` with ``dequant`` once
+    ``dequant_server_data()`` was called. Every other message passes unchanged in both directions
+    (the reference does not quantise a delta on the client), ``None`` included, and every other
+    attribute is the wrapped endpoint's. Keyword arguments ``device`` and ``out`` (both optional)
+    are passed to ``dequant`` where given: where to decode host records, and the tensors to decode
+    into, e.g. the model's own parameters. Without an ``endpoint`` the remaining keyword arguments
+    build the simulator's ``ClientEndpoint`` (the reference's base class), which is how
+    ``AlgorithmRepository.create_client`` constructs it."""
+
+    def __init__(self, quant: Callable[..., dict[str, Any]], dequant: Callable[..., dict[str, Any]],
+                 endpoint: Any = None, **kwargs: Any) -> None:
+        self.device: torch.device | str | None = kwargs.pop("device", None)
+        self.out: Mapping[str, torch.Tensor] | None = kwargs.pop("out", None)
+        if endpoint is None:
+            from cyy_naive_lib.topology.cs_endpoint import ClientEndpoint  # the simulator's, not vendored
+
+            endpoint = ClientEndpoint(**kwargs)
+        elif kwargs:
+            raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")
+        if not callable(getattr(endpoint, "send", None)) or not callable(getattr(endpoint, "get", None)):
+            raise TypeError("the wrapped endpoint needs a get() and a send(data) method")
+        self._endpoint = endpoint
+        self._quant = quant
+        self._dequant = dequant
+        self._dequant_server_data = False
+
+    def __getattr__(self, name: str) -> Any:  # only what this object does not have itself
+        endpoint = self.__dict__.get("_endpoint")
+        if endpoint is None:
+            raise AttributeError(name)
+        return getattr(endpoint, name)
+
+    def dequant_server_data(self) -> None:
+        self._dequant_server_data = True
+
+    def _quantize(self, parameter: Mapping[str, torch.Tensor]) -> dict[str, Any]:
+        return self._quant(parameter)
+
+    def _dequantize(self, parameter: Mapping[str, Any]) -> dict[str, Any]:
+        options = {k: v for k, v in (("device", self.device), ("out", self.out)) if v is not None}
+        return self._dequant(parameter, **options)
+
+    def get(self, *args: Any, **kwargs: Any) -> Any:
+        data = self._endpoint.get(*args, **kwargs)
+        if not self._dequant_server_data or data is None:
+            return data
+        if not is_parameter_message(data):  # the reference's assert isinstance(data, ParameterMessage)
+            raise AssertionError(f"a quantised broadcast is a ParameterMessage, not {type(data).__name__}")
+        data.parameter = self._dequantize(data.parameter)
+        return data
+
+    def send(self, data: Any) -> None:
+        if is_parameter_message(data):
+            data.parameter = self._quantize(data.parameter)
+            self._after_quant(data=data)
+            _log.debug("after client quantization")
+        self._endpoint.send(data)
+
+    def _after_quant(self, data: Any) -> None:
+        pass
+
+
+class _BroadcastCodecEndpoint(QuantClientEndpoint):
+    """A ``QuantClientEndpoint`` whose pair is a ``BroadcastQuantizer`` and a ``BroadcastDequantizer``:
+    an update on a GPU is encoded there by ``fedavg_quant_encode``, a host update by the numpy path
+    that gives the same bytes, and the records own their memory (the quantizer starts a new blob per
+    send). ``draw`` starts at 0 and advances by one per ``send``, so no two sends of an endpoint
+    share a stream of uniforms."""
+
+    def __init__(self, quantizer: BroadcastQuantizer, **kwargs: Any) -> None:
+        super().__init__(quant=quantizer, dequant=BroadcastDequantizer(), **kwargs)
+        self.draw = 0
+
+    def _next_draw(self) -> int:
+        draw = self.draw
+        self.draw = (draw + 1) & _U32
+        return draw
+
+    def _quantize(self, parameter: Mapping[str, torch.Tensor]) -> dict[str, Any]:
+        records = self._quant(parameter, self._next_draw())
+        self._quant.detach_blobs()  # the server may hold these records while the next update is encoded
+        return records
+
+
+class StochasticQuantClientEndpoint(_BroadcastCodecEndpoint):
+    """The reference's ``StochasticQuantClientEndpoint`` (quantized_endpoint.py:102-105): QSGD at
+    level 255 in both directions. Keyword argument ``seed`` (None: 64 bits of ``os.urandom`` per
+    endpoint; a fixed seed is for tests and reproducible experiments), then those of
+    ``QuantClientEndpoint``."""
+
+    def __init__(self, **kwargs: Any) -> None:
+        seed: int | None = kwargs.pop("seed", None)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        super().__init__(BroadcastQuantizer("qsgd", quantization_level=DEFAULT_LEVEL, seed=seed), **kwargs)
+
+    @property
+    def seed(self) -> int:
+        return self._quant.seed
+
+
+class NNADQClientEndpoint(_BroadcastCodecEndpoint):
+    """The reference's ``NNADQClientEndpoint`` (quantized_endpoint.py:114-124): NNADQ records with the
+    worker's ``weight`` going out, whatever NNADQ records the server sends coming in, and the
+    compression ratio logged after every quantisation. ``weight`` has no default."""
+
+    def __init__(self, weight: float, **kwargs: Any) -> None:
+        _log.debug("use weight %s", weight)
+        super().__init__(BroadcastQuantizer("nnadq", weight=weight), **kwargs)
+
+    def _after_quant(self, data: Any) -> None:
+        NeuralNetworkAdaptiveDeterministicQuant.check_compression_ratio(quantized_data=data, prefix="worker")

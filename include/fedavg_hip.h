@@ -147,7 +147,7 @@ int32_t fedavg_build_flags(void);
  * "route_chunk" (wanted ids per workgroup of the rank walk), "route_threads", "route_max_sources" and
  * "route_max_node_space" of fedavg_route_rows;
  * "quant_tile" (elements per workgroup), "quant_threads" and "quant_per_lane" (consecutive elements a
- * lane encodes) of fedavg_quant_encode;
+ * lane encodes) of fedavg_quant_encode, and of fedavg_quant_decode (a lane decodes as many);
  * "dp_tile" (elements per piece of a sum and per workgroup of the apply pass), "dp_threads" (lanes
  * that share a piece) and "dp_ae_<d>" (elements of one 16-byte group: what a lane adds in a row) of
  * fedavg_dp_noise;
@@ -724,6 +724,49 @@ int32_t fedavg_quant_encode(fedavg_ctx* ctx, int32_t codec, const void* const* i
                             const uint32_t* tensor_ids /* [T], host, or NULL: 0 .. T - 1 */,
                             int32_t num_tensors, void* const* record_ptrs /* [T], device */,
                             int32_t level, double weight, uint64_t seed, uint32_t draw, void* stream);
+
+/*
+ * The record decoder: the `get` half of the reference's QuantClientEndpoint
+ * (simulation_lib/topology/quantized_endpoint.py:32-39), which dequantises the server's broadcast on
+ * every worker, and the dequantisation of QuantServerEndpoint.get (:69-77) for consumers that take
+ * dense tensors. num_tensors QSGD or NNADQ records of one codec (the layouts of FEDAVG_QSGD_F32 /
+ * FEDAVG_NNADQ_F32 above) become dense tensors where they lie, in one launch. The contract is
+ * DESIGN.md §5u; the expected values are oracle/qsgd_oracle.py:dequantize and
+ * oracle/nnadq_oracle.py:dequantize.
+ *
+ * codec: FEDAVG_QSGD_F32 / QSGD_F64 / NNADQ_F32 / NNADQ_F64; the codec's dtype F (fp32 or fp64) is
+ * the outputs' dtype. record_ptrs[num_tensors] (host array of device pointers): 16-byte aligned
+ * records of numels[t] (host, >= 0) elements. out_ptrs[num_tensors]: numels[t] elements of F each,
+ * aligned to the element only (a model's parameters are arbitrary views): 16-byte stores are used
+ * where an address allows, single elements before and after, and the bits do not depend on which.
+ * out64_ptrs (NULL, or [num_tensors]; FEDAVG_QSGD_F32 and FEDAVG_NNADQ_F32 only): fp64 buffers of
+ * numels[t] elements, aligned to 8 bytes, that receive the exact widening of the same x in the same
+ * pass (the copy a worker's model cache keeps). A record, an output and a wide output may be NULL
+ * where numels[t] == 0. Outputs overlap neither each other nor the records.
+ *
+ * Every operation is separately rounded in F: no FMA, no reciprocal, IEEE division.
+ *   QSGD:  norm = F(header norm);  level = F(header level);  sign = +1 where the element's bit is
+ *          set, else -1;  a = norm * sign;  b = a * F(slot);  x = b / level
+ *   NNADQ: lo = F(header lo);  step = F(header step);  t = F(code) * step;  x = t + lo
+ * for every record byte pattern: slots above level, codes above levels and products that overflow
+ * decode by the same lines.
+ *
+ * One launch whatever num_tensors is, over tiles of "quant_tile" elements: a lane reads one 16-byte
+ * group of slots or codes and its 2 sign bytes, a workgroup its own record's header. No atomics, no
+ * host round trip: asynchronous on `stream`. Exactly numels[t] elements of every output are written
+ * and nothing else; the records are only read; the accumulator and its state are not touched.
+ * FEDAVG_FLAG_INPUT_NAN is latched (fedavg_check reports FEDAVG_ERR_NAN_INPUT) by a header whose
+ * level / levels lies outside [1, 255] and by a decoded element that is not finite; the outputs of
+ * such a call are unspecified but stay inside their buffers.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad codec; a NULL table; num_tensors < 1 or >
+ * 2^20; a negative count; a NULL or misaligned record; a NULL output or one not aligned to its
+ * element; out64_ptrs with an _F64 codec; more than 2^31 - 1 tiles), FEDAVG_ERR_STATE (an open
+ * dynamic wave).
+ */
+int32_t fedavg_quant_decode(fedavg_ctx* ctx, int32_t codec, const void* const* record_ptrs /* [T], device */,
+                            const int64_t* numels /* [T], host */, int32_t num_tensors,
+                            void* const* out_ptrs /* [T], device, dtype F */,
+                            void* const* out64_ptrs /* [T] or NULL, device, fp64 */, void* stream);
 
 /*
  * The clip-and-noise pass of the differential-privacy endpoints: the arithmetic of the reference's
