@@ -50,6 +50,19 @@ ACC_ALIGN = 32  # FEDAVG_ACC_ALIGN: accumulator segments start at multiples of 3
 BUILD_ABLATE_EPILOGUE = 0x1
 BUILD_ABLATE_QSGD = 0x2
 
+
+
+def record_bytes(code: int, numel: int) -> int:
+    """Byte size of the record of a ``numel``-element tensor in record format ``code`` (the package's
+    one host definition of ``fedavg_qsgd_record_bytes`` / ``fedavg_nnadq_record_bytes``): a 16-byte
+    (QSGD) or 32-byte (NNADQ) header, one level byte per element and, for QSGD, one sign bit per
+    element, each part padded to a multiple of 16 bytes."""
+    levels = (numel + 15) // 16 * 16
+    if code in (NNADQ_F32, NNADQ_F64):
+        return 32 + levels
+    return 16 + levels + ((numel + 7) // 8 + 15) // 16 * 16
+
+
 _PP = POINTER(c_void_p)
 _PD = POINTER(c_double)
 

@@ -11,7 +11,7 @@ NOT an algorithm of the reference (it aggregates with the weighted mean only). T
 * ``f = num_byzantine`` (``None``: ``(n - 3) // 4``, the most the round allows), ``theta = n - 2f``
   updates are selected and ``beta = theta - 2f`` values averaged per coordinate. ``n < 4f + 3`` is a
   ``ValueError``; ``n > 256`` or ``theta > 64`` a ``NotImplementedError``.
-* ``D`` is Krum's matrix of squared distances (§5h), ``fedavg.bulyan_select(D, f)`` the selection:
+* ``D`` is Krum's matrix of squared distances (§5h), ``rules.bulyan_select(D, f)`` the selection:
   ``theta`` times the row of the remaining ones with the smallest Krum score among them leaves
   (``max(1, r - f - 2)`` neighbours at ``r`` remaining rows — the paper's count runs out in the
   last picks, and this project then scores a row by its nearest neighbour; ties to the earlier
@@ -40,9 +40,10 @@ from typing import NamedTuple
 
 import torch
 
-from ..fedavg import NaNAggregationError, bulyan_select
+from ..fedavg import NaNAggregationError
 from .._native import KRUM_MAX_CLIENTS, ROBUST_MAX_CLIENTS
 from ..message import ModelParameter
+from ..rules import bulyan_select
 from .aggregation_algorithm import fill_empty
 from .dense_round import DenseRoundAlgorithm, _GpuRound, pairwise_sqdist_cpu
 from .robust_aggregation_algorithm import _total_order_sort

@@ -22,7 +22,7 @@ client's whole update to one fp64 point is ``fedavg_sqdist_to_point``; the step
    the layout: a ``ValueError`` names the key); with ``start="mean"`` the FedAvg of the kept clients
    with the weights ``alpha``.
 4. For ``l = 1 .. iterations``: ``D_i = sum_e (x_i[e] - v_{l-1}[e])^2`` in the pinned order of §5i;
-   ``(coef, clipped) = fedavg.clipping_coefficients(D, alpha, radius)``, that is
+   ``(coef, clipped) = rules.clipping_coefficients(D, alpha, radius)``, that is
    ``coef_i = alpha_i * (1 if sqrt(D_i) <= radius else radius / sqrt(D_i))``; per element
    ``d_i = x_i - v``, ``p_i = coef_i * d_i``, ``acc = p_0 + p_1 + ...`` in arrival order,
    ``r = acc / W``, ``v_l = v_{l-1} + r``: five separately rounded float64 operations. The last
@@ -47,9 +47,9 @@ from typing import NamedTuple
 
 import torch
 
-from ..fedavg import clipping_coefficients
 from .._native import POINT_MAX_CLIENTS
 from ..message import ModelParameter
+from ..rules import clipping_coefficients
 from .dense_round import DenseRoundAlgorithm, _CpuRound, _GpuRound, finite_screen
 
 STARTS = ("previous", "mean")

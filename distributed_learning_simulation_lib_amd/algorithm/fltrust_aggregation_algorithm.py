@@ -31,7 +31,7 @@ independently):
    centre raises ``NaNAggregationError`` (stage ``input``); a NaN moment (stage ``accumulator``)
    needs ``inf - inf`` or ``0 * inf``, which the screen leaves no way to. An infinity in the centre
    makes every squared norm ``+inf``: every client is distrusted and step 7 raises.
-7. ``(score, coef) = fedavg.trust_coefficients(T, S, root_sqnorm)``: ``n0 = sqrt(root_sqnorm)``,
+7. ``(score, coef) = rules.trust_coefficients(T, S, root_sqnorm)``: ``n0 = sqrt(root_sqnorm)``,
    ``ni = sqrt(S_i)``, ``den = ni * n0``; ``S_i`` not finite or ``den == 0``: distrusted (0.0, 0.0);
    otherwise ``cos = T_i / den``, ``score = cos if cos > 0 else 0.0``,
    ``coef = score * (n0 / ni)``. ``W`` is the sum of the non-root scores, added in arrival order;
@@ -56,9 +56,10 @@ from typing import NamedTuple
 
 import torch
 
-from ..fedavg import ModelLayout, NaNAggregationError, trust_coefficients
+from ..fedavg import ModelLayout, NaNAggregationError
 from .._native import POINT_MAX_CLIENTS
 from ..message import ModelParameter
+from ..rules import trust_coefficients
 from .dense_round import _DTYPE_TAGS, DenseRoundAlgorithm, _CpuRound, _GpuRound, finite_screen
 
 # the kernel's geometry where the native library cannot be asked (§5i's)

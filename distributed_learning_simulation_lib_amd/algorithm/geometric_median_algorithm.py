@@ -20,7 +20,7 @@ independently):
 3. ``z_0`` is the FedAvg of the kept clients with the weights ``alpha``, in float64.
 4. For ``t = 1 .. max_iterations``: ``D_i = sum_e (x_i[e] - z_{t-1}[e])^2`` (values converted exactly
    to float64; subtract, square and add each rounded in float64, in the pinned order of §5i);
-   ``(beta, G_{t-1}) = fedavg.geometric_median_step(D, alpha, smoothing)``, that is
+   ``(beta, G_{t-1}) = rules.geometric_median_step(D, alpha, smoothing)``, that is
    ``beta_i = alpha_i / max(smoothing, sqrt(D_i))`` and ``G = sum_i alpha_i sqrt(D_i)``. If
    ``tolerance > 0``, ``t >= 2`` and ``|G_{t-2} - G_{t-1}| <= tolerance * G_{t-1}``, stop with
    ``z_{t-1}``. Otherwise ``z_t`` is the FedAvg of the kept clients with the weights ``beta``; if
@@ -47,9 +47,9 @@ from typing import NamedTuple
 
 import torch
 
-from ..fedavg import geometric_median_step
 from .._native import POINT_MAX_CLIENTS
 from ..message import ModelParameter
+from ..rules import geometric_median_step
 from .dense_round import (  # noqa: F401  (the distance's home is dense_round; the names stay importable here)
     POINT_DEFAULTS,
     DenseRoundAlgorithm,

@@ -43,9 +43,9 @@ from typing import NamedTuple
 
 import torch
 
-from ..fedavg import krum_select
 from .._native import KRUM_MAX_CLIENTS
 from ..message import ModelParameter
+from ..rules import krum_select
 from .aggregation_algorithm import fill_empty
 from .dense_round import DenseRoundAlgorithm, _GpuRound, pairwise_sqdist_cpu, weighted_mean_cpu
 

@@ -29,9 +29,10 @@ from __future__ import annotations
 
 import torch
 
-from ..fedavg import ClientTable, ModelLayout, NaNAggregationError, check_robust_rule, robust_trim
+from ..fedavg import ClientTable, ModelLayout, NaNAggregationError
 from .._native import ROBUST_MAX_CLIENTS
 from ..message import ModelParameter
+from ..rules import check_robust_rule, robust_trim
 from .aggregation_algorithm import context_for, fill_empty, split_empty, to_device_operand, unify_dtype
 from .dense_round import DenseRoundAlgorithm
 

@@ -19,7 +19,7 @@ owns. The contract (``tests/opt_reference.py`` restates it indep
    float64 operation (no FMA, no reciprocal, a correctly rounded square root, no bias correction):
    ``d_i = x_i - z``, ``p_i = c_i * d_i``, ``acc = p_0 + p_1 + ...`` in arrival order,
    ``delta = acc / W`` — so far ``fedavg_fold_about_point`` — then
-   ``fedavg.server_opt_update``'s lines for the optimiser (``m' = beta1 * m + delta`` for ``"avgm"``,
+   ``rules.server_opt_update``'s lines for the optimiser (``m' = beta1 * m + delta`` for ``"avgm"``,
    ``m' = beta1 * m + (1 - beta1) * delta`` and the second moment's rule for the others),
    ``u = lr * m'`` (``"avgm"``) or ``(lr * m') / (sqrt(v') + tau)``, ``out = z + u`` written in
    ``out_dtype`` (float32: that float64 result rounded to nearest even).
@@ -53,15 +53,10 @@ from typing import Any, NamedTuple
 
 import torch
 
-from ..fedavg import (
-    SERVER_OPT_MODES,
-    ModelLayout,
-    NaNAggregationError,
-    check_server_opt,
-    server_opt_update,
-)
 from .._native import POINT_MAX_CLIENTS
+from ..fedavg import ModelLayout, NaNAggregationError
 from ..message import ModelParameter
+from ..rules import SERVER_OPT_MODES, check_server_opt, server_opt_update
 from .dense_round import DenseRoundAlgorithm, _CpuRound, _GpuRound
 
 

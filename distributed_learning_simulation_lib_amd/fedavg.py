@@ -9,7 +9,13 @@ finalize/NaN checks (``fed_avg_algorithm.py:76-99``).
 
 Every method launches asynchronously on the current torch stream of the context's device
 (``torch.cuda.current_stream``); PyTorch is only the allocator and stream provider here. The
-arithmetic runs in the HIP kernels of ``csrc/fedavg_kernels.hip``; there is no CPU path.
+device arithmetic runs in the HIP kernels of ``csrc/``; a missing kernel is an error, never a quiet
+CPU fall-back. The host arithmetic that the side rules do between two kernel calls (and that the
+algorithms' own CPU paths share) lives in ``rules.py`` and is re-exported here.
+
+The side-kernel wrappers of ``FedAvgContext`` (``robust_aggregate`` to ``server_opt_step``) refuse
+every operand a kernel would read or write out of bounds before anything is launched; the checks
+they share are the private helpers above them.
 """
 
 from __future__ import annotations
@@ -26,6 +32,10 @@ import numpy as np
 import torch
 
 from . import _native
+from .rules import (  # noqa: F401 - re-exported: ``from ...fedavg import krum_select`` keeps working
+    ROBUST_MODES, SERVER_OPT_MODES, _sqrt_rn, bulyan_select, check_robust_rule, check_server_opt,
+    clipping_coefficients, geometric_median_step, krum_select, robust_trim, server_opt_update, trust_coefficients,
+)
 from .sparse import SparseDelta
 
 DTYPE_CODES: dict[torch.dtype, int] = {
@@ -147,23 +157,6 @@ def out_code(dtype: torch.dtype) -> int:
         raise TypeError(f"aggregated output dtype must be float32 or float64, not {dtype}") from None
 
 
-ROBUST_MODES = ("trimmed_mean", "median")
-
-
-def check_robust_rule(mode: str, trim: float) -> None:
-    """ValueError for an unknown robust rule or a trim fraction outside [0, 0.5)."""
-    if mode not in ROBUST_MODES:
-        raise ValueError(f"robust aggregation mode must be one of {ROBUST_MODES}, not {mode!r}")
-    if mode == "trimmed_mean" and not 0 <= trim < 0.5:  # NaN fails it too
-        raise ValueError(f"trim must satisfy 0 <= trim < 0.5 (the kept range must not be empty), not {trim}")
-
-
-def robust_trim(mode: str, trim: float, n: int) -> int:
-    """Values dropped at each end of a tensor's n sorted client values: floor(trim * n) for the
-    trimmed mean; (n - 1) // 2 for the median, which leaves the one or two middle values."""
-    return (n - 1) // 2 if mode == "median" else math.floor(trim * n)
-
-
 def robust_trim_counts(table: ClientTable, mode: str, trim: float) -> list[int]:
     """Per segment k for the table's clients, after the refusals that need no device."""
     check_robust_rule(mode, trim)
@@ -181,239 +174,6 @@ def robust_trim_counts(table: ClientTable, mode: str, trim: float) -> list[int]:
             raise ValueError(f"tensor {t} was sent by no client")
         ks.append(robust_trim(mode, trim, n))
     return ks
-
-
-def krum_select(D: Any, f: int, m: int) -> tuple[list[float], list[int]]:
-    """Krum scores and the one-shot Multi-Krum choice from the n x n matrix of squared distances
-    (host arithmetic in fp64, shared by the GPU and the CPU path).
-
-    ``f`` is the assumed number of Byzantine clients (``n >= 2f + 3``). ``score_i`` is the sum of
-    the ``n - f - 2`` smallest ``D[i][j]``, ``j != i``: sorted ascending, ties in ascending ``j``,
-    added sequentially from the smallest. The ``m`` rows (``1 <= m <= n - f``; 1 is Krum) with the
-    smallest ``(score, row)`` are chosen, so ties go to the earlier arrival. Returns
-    ``(scores, chosen_rows)``, the rows in ascending order (arrival order)."""
-    rows = [[float(x) for x in r] for r in (D.tolist() if hasattr(D, "tolist") else D)]
-    n = len(rows)
-    if any(len(r) != n for r in rows):
-        raise ValueError("the distance matrix must be square")
-    f, m = int(f), int(m)
-    if f < 0 or n < 2 * f + 3:
-        raise ValueError(f"Krum needs n >= 2f + 3 clients: n = {n}, f = {f}")
-    if not 1 <= m <= n - f:
-        raise ValueError(f"Multi-Krum selects 1 <= m <= n - f = {n - f} clients, not {m}")
-    keep = n - f - 2
-    scores = []
-    for i, r in enumerate(rows):
-        near = sorted((d, j) for j, d in enumerate(r) if j != i)[:keep]
-        s = 0.0
-        for d, _ in near:
-            s = s + d
-        scores.append(s)
-    order = sorted(range(n), key=lambda i: (scores[i], i))
-    return scores, sorted(order[:m])
-
-
-def bulyan_select(D: Any, f: int) -> tuple[list[int], list[float]]:
-    """Bulyan's selection from the n x n matrix of squared distances (host arithmetic
-    in plain Python floats, shared by the GPU and the CPU path): Krum applied iteratively.
-
-    ``f`` is the assumed number of Byzantine clients (``n >= 4f + 3``); ``theta = n - 2f`` rows are
-    picked. Start from R, all rows, and repeat ``theta`` times with ``r = |R|``: if ``r == 1`` the
-    row that is left is taken with score 0.0; otherwise, with ``c = max(1, r - f - 2)``,
-    ``score_i`` (i in R) is the sum of the ``c`` smallest ``D[i][j]``, j in R without i — sorted
-    ascending, ties in ascending ``j``, added sequentially from the smallest starting at 0.0 — and
-    the row with the smallest ``(score, row)`` is picked and leaves R, so ties go to the earlier
-    arrival. The ``max(1, .)`` is this project's choice: the paper's ``r - f - 2`` neighbours run
-    out in the last picks (``r`` goes down to ``2f + 1``, where ``r - f - 2 = f - 1`` is 0 for
-    ``f = 1`` and all of R is picked for ``f = 0``), and a row is then judged by its nearest
-    neighbour. Returns ``(picked_rows, pick_scores)``: the rows in pick order and the winning
-    score of each pick."""
-    rows = [[float(x) for x in r] for r in (D.tolist() if hasattr(D, "tolist") else D)]
-    n = len(rows)
-    if any(len(r) != n for r in rows):
-        raise ValueError("the distance matrix must be square")
-    f = int(f)
-    if f < 0 or n < 4 * f + 3:
-        raise ValueError(f"Bulyan needs n >= 4f + 3 clients: n = {n}, f = {f}")
-    # every row's neighbours once, nearest first; a pick only removes entries from these lists
-    near = [sorted((d, j) for j, d in enumerate(r) if j != i) for i, r in enumerate(rows)]
-    alive = [True] * n
-    picked: list[int] = []
-    scores: list[float] = []
-    for r in range(n, 2 * f, -1):
-        best: tuple[float, int] | None = None
-        if r == 1:
-            best = (0.0, alive.index(True))
-        else:
-            c = max(1, r - f - 2)
-            for i in range(n):
-                if not alive[i]:
-                    continue
-                s, left = 0.0, c
-                for d, j in near[i]:
-                    if alive[j]:
-                        s = s + d
-                        left -= 1
-                        if left == 0:
-                            break
-                if best is None or (s, i) < best:
-                    best = (s, i)
-        assert best is not None
-        scores.append(best[0])
-        picked.append(best[1])
-        alive[best[1]] = False
-    return picked, scores
-
-
-def geometric_median_step(dist_sq: Sequence[float], alpha: Sequence[float],
-                          smoothing: float) -> tuple[list[float], float]:
-    """One smoothed Weiszfeld step of the geometric median (host arithmetic in plain
-    Python floats, shared by the GPU and the CPU path): from the clients' squared distances ``D_i``
-    to the current point and their weights ``alpha_i``, with ``d_i = math.sqrt(D_i)``, the next
-    fold's weights ``beta_i = alpha_i / max(smoothing, d_i)`` and the objective
-    ``sum_i alpha_i * d_i`` at the current point, added sequentially in arrival order from 0.0.
-    Returns ``(beta, objective)``."""
-    ds = [float(x) for x in (dist_sq.tolist() if hasattr(dist_sq, "tolist") else dist_sq)]
-    al = [float(a) for a in alpha]
-    nu = float(smoothing)
-    if len(ds) != len(al):
-        raise ValueError("one squared distance per weight is required")
-    if not nu > 0:
-        raise ValueError(f"smoothing must be > 0, not {smoothing}")
-    beta, objective = [], 0.0
-    for D, a in zip(ds, al):
-        d = math.sqrt(D)
-        beta.append(a / max(nu, d))
-        objective = objective + a * d
-    return beta, objective
-
-
-def clipping_coefficients(dist_sq: Sequence[float], alpha: Sequence[float],
-                          radius: float) -> tuple[list[float], int]:
-    """The coefficients of one centred-clipping step (host arithmetic in plain Python
-    floats, shared by the GPU and the CPU path): from the clients' squared distances ``D_i`` to the
-    current centre and their weights ``alpha_i``, with ``d_i = math.sqrt(D_i)``,
-    ``c_i = 1.0 if d_i <= radius else radius / d_i`` (``D_i = +inf`` gives 0.0) and
-    ``coef_i = alpha_i * c_i``. Returns ``(coef, clipped)``: the coefficients and the number of
-    clients whose distance exceeded the radius."""
-    ds = [float(x) for x in (dist_sq.tolist() if hasattr(dist_sq, "tolist") else dist_sq)]
-    al = [float(a) for a in alpha]
-    tau = float(radius)
-    if len(ds) != len(al):
-        raise ValueError("one squared distance per weight is required")
-    if not (tau > 0 and math.isfinite(tau)):
-        raise ValueError(f"radius must be a finite number > 0, not {radius}")
-    coef, clipped = [], 0
-    for D, a in zip(ds, al):
-        d = math.sqrt(D)
-        if d <= tau:
-            c = 1.0
-        else:
-            c = tau / d
-            clipped += 1
-        coef.append(a * c)
-    return coef, clipped
-
-
-def trust_coefficients(dots: Sequence[float], sqnorms: Sequence[float],
-                       root_sqnorm: float) -> tuple[list[float], list[float]]:
-    """FLTrust's trust scores and coefficients (host arithmetic in plain Python
-    floats, shared by the GPU and the CPU path): from the clients' dots ``T_i = <x_i - v, g>`` with
-    the root direction, their squared norms ``S_i = |x_i - v|^2`` and the root's own squared norm,
-    in this operation order: ``n0 = math.sqrt(root_sqnorm)``, ``ni = math.sqrt(S_i)``,
-    ``den = ni * n0``; a client whose ``S_i`` is not finite or whose ``den`` is 0 is distrusted
-    (score and coefficient 0.0); otherwise ``cos = T_i / den``, ``score = cos if cos > 0 else 0.0``
-    (the ReLU-clipped cosine; a NaN cosine scores 0.0) and ``coefficient = score * (n0 / ni)`` (the
-    score times the rescaling of the client's update to the root's norm). Returns
-    ``(scores, coefficients)``."""
-    ts = [float(x) for x in (dots.tolist() if hasattr(dots, "tolist") else dots)]
-    ss = [float(x) for x in (sqnorms.tolist() if hasattr(sqnorms, "tolist") else sqnorms)]
-    root = float(root_sqnorm)
-    if len(ts) != len(ss):
-        raise ValueError("one dot per squared norm is required")
-    n0 = math.sqrt(root)
-    scores, coef = [], []
-    for T, S in zip(ts, ss):
-        if not math.isfinite(S):
-            scores.append(0.0)
-            coef.append(0.0)
-            continue
-        ni = math.sqrt(S)
-        den = ni * n0
-        if den == 0:
-            scores.append(0.0)
-            coef.append(0.0)
-            continue
-        cos = T / den
-        score = cos if cos > 0 else 0.0
-        scores.append(score)
-        coef.append(score * (n0 / ni))
-    return scores, coef
-
-
-SERVER_OPT_MODES = ("avgm", "adagrad", "yogi", "adam")  # FEDAVG_OPT_AVGM / ADAGRAD / YOGI / ADAM in this order
-
-
-def check_server_opt(mode: str, lr: float, beta1: float, beta2: float,
-                     tau: float) -> tuple[int, float, float, float, float, float, float]:
-    """The hyper-parameters of a server optimiser step, validated as the C call
-    validates them: ``mode`` one of ``SERVER_OPT_MODES``; ``lr`` finite and > 0; ``beta1`` and
-    ``beta2`` in [0, 1); ``tau`` finite and > 0 in the adaptive modes (``"avgm"`` ignores it).
-    Returns ``(code, lr, beta1, 1 - beta1, beta2, 1 - beta2, tau)`` as Python floats: ``1 - beta`` is
-    computed here once, so the kernel, the CPU path and a restatement use the same doubles."""
-    if mode not in SERVER_OPT_MODES:
-        raise ValueError(f"mode must be one of {SERVER_OPT_MODES}, not {mode!r}")
-    lr, beta1, beta2, tau = float(lr), float(beta1), float(beta2), float(tau)
-    if not (lr > 0 and math.isfinite(lr)):
-        raise ValueError(f"the learning rate must be a finite number > 0, not {lr}")
-    for name, b in (("beta1", beta1), ("beta2", beta2)):
-        if not 0 <= b < 1:
-            raise ValueError(f"{name} must lie in [0, 1), not {b}")
-    if mode != "avgm" and not (tau > 0 and math.isfinite(tau)):
-        raise ValueError(f"tau must be a finite number > 0, not {tau}")
-    return SERVER_OPT_MODES.index(mode), lr, beta1, 1.0 - beta1, beta2, 1.0 - beta2, tau
-
-
-def _sqrt_rn(t: torch.Tensor) -> torch.Tensor:
-    """The correctly rounded float64 square root of a CPU tensor. ``torch.sqrt``'s CPU kernel goes
-    through a vector maths library whose results are off by one ulp for some inputs (measured: 670
-    of 100 000 uniform values against ``numpy.sqrt``), so the root — and it alone — is taken by numpy,
-    which uses the processor's IEEE instruction."""
-    with np.errstate(invalid="ignore"):
-        r = np.sqrt(t.detach().contiguous().numpy().reshape(-1))
-    return torch.from_numpy(r).reshape(t.shape)
-
-
-def server_opt_update(mode: str, delta: torch.Tensor, m: torch.Tensor, v: torch.Tensor | None, lr: float,
-                      beta1: float, one_minus_beta1: float, beta2: float, one_minus_beta2: float,
-                      tau: float) -> tuple[torch.Tensor, torch.Tensor | None, torch.Tensor]:
-    """The optimiser lines of ``fedavg_server_opt_step`` in torch, one float64 operation per line
-    (DESIGN.md §5m): from the pseudo-gradient ``delta`` and the moments ``m``, ``v`` returns
-    ``(m', v', u)``; the new model is ``z + u``. ``v`` and ``v'`` are ``None`` for ``"avgm"``. CPU
-    tensors only (the square root is ``_sqrt_rn``)."""
-    a = beta1 * m
-    if mode == "avgm":
-        m_new = a + delta
-        return m_new, None, lr * m_new
-    b = one_minus_beta1 * delta
-    m_new = a + b
-    q = delta * delta
-    if mode == "adagrad":
-        v_new = v + q
-    elif mode == "adam":
-        e = beta2 * v
-        f = one_minus_beta2 * q
-        v_new = e + f
-    else:  # yogi
-        g = v - q
-        s = (g > 0).to(torch.float64) - (g < 0).to(torch.float64)  # +1.0, -1.0, else (NaN included) +0.0
-        f = one_minus_beta2 * q
-        h = f * s
-        v_new = v - h
-    r = _sqrt_rn(v_new)
-    den = r + tau
-    num = lr * m_new
-    return m_new, v_new, num / den
 
 
 class ClientTable:
@@ -644,6 +404,59 @@ class SparseTable:
         self._keep = [list(row) for row in rows]
 
 
+NOT_IN_PLACE = "the step is not in-place, ping-pong two buffers"
+
+
+def _pointer_array(tensors: Sequence[torch.Tensor]) -> ctypes.Array:
+    return (ctypes.c_void_p * len(tensors))(*[z.data_ptr() for z in tensors])
+
+
+def _first(T: int, *faults: int) -> tuple[int, int]:
+    """Which refusal a call over T tensors reports. Each of ``faults`` is the first tensor at which
+    one kind of fault holds (T: nowhere), the kinds in the order in which one tensor is checked.
+    Returns ``(t, kind)`` of the first fault in tensor order, ``(T, -1)`` if there is none."""
+    t = min(faults)
+    return (t, faults.index(t)) if t < T else (T, -1)
+
+
+def _first_shared(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor]) -> int:
+    """The first index at which ``a`` and ``b`` hold the same storage address; ``len(a)`` if none."""
+    return next((t for t, (x, y) in enumerate(zip(a, b)) if x.data_ptr() == y.data_ptr()), len(a))
+
+
+def _addresses(tensors: Sequence[torch.Tensor | None], counts: Sequence[int]) -> np.ndarray:
+    """The C-ABI address table of a layout-free call: 0 for an absent or an empty (``counts[t] == 0``) tensor."""
+    return np.array([z.data_ptr() if z is not None and n else 0 for z, n in zip(tensors, counts)], dtype=np.uint64)
+
+
+def _client_scalars(values: Sequence[float], n: int, what: str) -> np.ndarray:
+    """One finite fp64 ``what`` ("coefficient", "weight") per client, as the C-ABI array."""
+    v = np.ascontiguousarray([float(x) for x in values], dtype=np.float64)
+    if v.shape != (n,):
+        raise ValueError(f"one {what} per client is required: {v.size} for {n} clients")
+    if not np.isfinite(v).all():
+        raise ValueError(f"the {what}s must be finite")
+    return v
+
+
+def _divisor(divisor: float) -> float:
+    divisor = float(divisor)
+    if not (divisor > 0 and math.isfinite(divisor)):
+        raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
+    return divisor
+
+
+def _stream_ids(seed: int, draw: int, tensor_ids: Sequence[int] | None, T: int) -> np.ndarray:
+    """The random stream's words of a call over T tensors: the seed and the draw in range, then one
+    uint32 id per tensor (default: its position)."""
+    if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
+        raise ValueError("the seed is a uint64 and the draw a uint32")
+    ids = np.arange(T, dtype=np.uint32) if tensor_ids is None else np.ascontiguousarray(tensor_ids, dtype=np.uint32)
+    if ids.shape != (T,):
+        raise ValueError("one stream id per tensor is required")
+    return ids
+
+
 class FedAvgContext:
     """One native FedAvg context: layout + device + fp64 accumulator."""
 
@@ -858,6 +671,93 @@ class FedAvgContext:
             )
         )
 
+    # -- what the side wrappers refuse, each check once ----------------------------
+    # These refusals are all that keeps an undersized or misplaced operand from a kernel that would
+    # read or write it out of bounds. ``what`` is the call's noun phrase, ``s`` its verb ending.
+    def _refuse_records(self, in_dtype: torch.dtype, what: str, s: str) -> None:
+        if dtype_code(in_dtype) in _native.RECORD_CODES:
+            raise NotImplementedError(f"{what} read{s} dense tensors: dequantise records first")
+
+    def _refuse_before_table(self, table: ClientTable, in_dtype: torch.dtype, what: str, s: str, limit: int) -> None:
+        """A whole-update call's refusals that come before the table check: an empty table, more
+        than ``limit`` clients, quantised records."""
+        if table.num_clients == 0:
+            raise ValueError(f"{what} of no clients")
+        if table.num_clients > limit:
+            raise NotImplementedError(f"{table.num_clients} clients: {what} take{s} at most {limit}")
+        self._refuse_records(in_dtype, what, s)
+
+    def _whole_updates(self, table: ClientTable, in_dtype: torch.dtype, whole: str) -> np.ndarray:
+        """The table check, then the first absent entry refused (the call ``whole``, as in
+        "distances compare", whole updates). Returns the table's pointer array."""
+        self._check_table(table, in_dtype)
+        n, T = table.num_clients, table.num_segments
+        p, _ = table.arrays()
+        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
+        if len(absent):
+            k, t = (int(x) for x in absent[0])
+            raise ValueError(f"client {k} lacks tensor {t}: {whole} whole updates")
+        return p
+
+    def _first_unfit(self, tensors: Sequence[torch.Tensor | None], dtype: torch.dtype,
+                     sizes: Sequence[int] | None = None) -> int:
+        """The index of the first of ``tensors`` that is not a contiguous ``dtype`` tensor (of
+        ``sizes[t]`` elements) on the context's device; ``len(tensors)`` if every one is. ``None``
+        entries are skipped. One loop per group and no call per tensor: a model has tens of tensors."""
+        device = self.device
+        if sizes is None:
+            for t, z in enumerate(tensors):
+                if z.dtype != dtype or z.device != device or not z.is_contiguous():
+                    return t
+        else:
+            for t, (z, size) in enumerate(zip(tensors, sizes)):
+                if z is not None and (z.dtype != dtype or z.device != device or z.numel() != size
+                                      or not z.is_contiguous()):
+                    return t
+        return len(tensors)
+
+    def _segment_refusal(self, what: str, t: int, dtype: torch.dtype | None = None) -> ValueError:
+        """For a per-segment group's tensor ``t``: fp64, or the outputs' ``dtype``."""
+        return ValueError(f"{what} tensor {t}: contiguous {dtype or 'fp64'} of {self.layout.numels[t]} elements on "
+                          f"{self.device} is required")
+
+    def _flat_refusal(self, what: str, t: int, dtype: torch.dtype, numel: int | None = None) -> ValueError:
+        """For a layout-free call's operand ``t``."""
+        size = "" if numel is None else f" of {numel} elements"
+        return ValueError(f"{what} {t}: a contiguous {dtype} tensor{size} on {self.device} is required")
+
+    def _record_refusal(self, t: int, need: int) -> ValueError:
+        return ValueError(f"record {t}: a contiguous uint8 tensor of {need} bytes on {self.device} is required")
+
+    def _segment_array(self, what: str, tensors: Sequence[torch.Tensor]) -> ctypes.Array:
+        """The pointer array of one contiguous fp64 tensor per segment on the context's device."""
+        T = self.layout.num_segments
+        if len(tensors) != T:
+            raise ValueError(f"one {what} tensor per segment is required")
+        t = self._first_unfit(tensors, torch.float64, self.layout.numels)
+        if t < T:
+            raise self._segment_refusal(what, t)
+        return _pointer_array(tensors)
+
+    def _source_and_outputs(self, what: str, src: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                            out_dtype: torch.dtype, why: str) -> tuple[ctypes.Array, ctypes.Array]:
+        """The pointer arrays of the fp64 ``what`` ("point", "base") tensors and of the outputs: one
+        contiguous ``out_dtype`` tensor per segment, none of them its source's own storage."""
+        T, numels = self.layout.num_segments, self.layout.numels
+        if len(src) != T or len(outs) != T:
+            raise ValueError(f"one {what} tensor and one output tensor per segment are required")
+        zs, os_ = [z.data_ptr() for z in src], [o.data_ptr() for o in outs]
+        t, fault = _first(T, self._first_unfit(src, torch.float64, numels), self._first_unfit(outs, out_dtype, numels),
+                          next((t for t in range(T) if zs[t] == os_[t]), T))
+        if fault == 0:
+            raise self._segment_refusal(what, t)
+        if fault == 1:
+            raise self._segment_refusal("output", t, out_dtype)
+        if fault == 2:
+            raise ValueError(f"output tensor {t} is its {what}: {why}")
+        return (ctypes.c_void_p * T)(*zs), (ctypes.c_void_p * T)(*os_)
+
+    # -- the side kernels --------------------------------------------------------------------------
     def robust_aggregate(
         self,
         table: ClientTable,
@@ -874,8 +774,7 @@ class FedAvgContext:
         rules are unweighted. Refused before any launch: ``trim`` outside [0, 0.5), a tensor sent
         by more than 64 clients, quantised records."""
         k_per_seg = robust_trim_counts(table, mode, trim)
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("robust aggregation reads dense tensors: dequantise records first")
+        self._refuse_records(in_dtype, "robust aggregation", "s")
         self._check_table(table, in_dtype)
         p, _ = table.arrays()
         ot = self._out_table(outs, out_dtype)
@@ -912,8 +811,7 @@ class FedAvgContext:
         for t, (k, n) in enumerate(zip(keeps, (int(x) for x in sent))):
             if not 1 <= k <= n:
                 raise ValueError(f"tensor {t}: keep {k} is not in [1, {n}]")
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("the mean around the median reads dense tensors: dequantise records first")
+        self._refuse_records(in_dtype, "the mean around the median", "s")
         self._check_table(table, in_dtype)
         p, _ = table.arrays()
         ot = self._out_table(outs, out_dtype)
@@ -932,19 +830,8 @@ class FedAvgContext:
         on the diagonal, the same bits on every run. The table's weights are ignored and the
         accumulator is not touched. Refused before any launch: an empty table, more than 256
         clients, an absent entry (distances compare whole updates), quantised records."""
-        if table.num_clients == 0:
-            raise ValueError("pairwise distances of no clients")
-        if table.num_clients > _native.KRUM_MAX_CLIENTS:
-            raise NotImplementedError(
-                f"{table.num_clients} clients: pairwise distances take at most {_native.KRUM_MAX_CLIENTS}")
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("pairwise distances read dense tensors: dequantise records first")
-        self._check_table(table, in_dtype)
-        p, _ = table.arrays()
-        absent = np.argwhere(np.asarray(p).reshape(table.num_clients, table.num_segments) == 0)
-        if len(absent):
-            k, t = (int(x) for x in absent[0])
-            raise ValueError(f"client {k} lacks tensor {t}: distances compare whole updates")
+        self._refuse_before_table(table, in_dtype, "pairwise distances", "", _native.KRUM_MAX_CLIENTS)
+        p = self._whole_updates(table, in_dtype, "distances compare")
         n = table.num_clients
         out = torch.empty((n, n), dtype=torch.float64, device=self.device)
         _native.check(
@@ -964,28 +851,9 @@ class FedAvgContext:
         same bits on every run, whatever the other clients of the table. The table's weights are
         ignored and the accumulator is not touched. Refused before any launch: an empty table, more
         than 1024 clients, an absent entry, quantised records, a point that does not match."""
-        if table.num_clients == 0:
-            raise ValueError("distances to a point of no clients")
-        if table.num_clients > _native.POINT_MAX_CLIENTS:
-            raise NotImplementedError(
-                f"{table.num_clients} clients: distances to a point take at most {_native.POINT_MAX_CLIENTS}")
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("distances to a point read dense tensors: dequantise records first")
-        self._check_table(table, in_dtype)
-        p, _ = table.arrays()
-        absent = np.argwhere(np.asarray(p)[: table.num_clients * table.num_segments]
-                             .reshape(table.num_clients, table.num_segments) == 0)
-        if len(absent):
-            k, t = (int(x) for x in absent[0])
-            raise ValueError(f"client {k} lacks tensor {t}: distances compare whole updates")
-        zp = None
-        if point is not None:
-            if len(point) != self.layout.num_segments:
-                raise ValueError("one point tensor per segment is required")
-            for t, (z, numel) in enumerate(zip(point, self.layout.numels)):
-                if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
-                    raise ValueError(f"point tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
-            zp = (ctypes.c_void_p * len(point))(*[z.data_ptr() for z in point])
+        self._refuse_before_table(table, in_dtype, "distances to a point", "", _native.POINT_MAX_CLIENTS)
+        p = self._whole_updates(table, in_dtype, "distances compare")
+        zp = None if point is None else self._segment_array("point", point)
         n = table.num_clients
         out = torch.empty(n, dtype=torch.float64, device=self.device)
         _native.check(
@@ -1010,39 +878,18 @@ class FedAvgContext:
         weights are ignored and the accumulator is not touched. Refused before any launch: an empty
         table, more than 1024 clients, an absent entry, quantised records, a centre or a direction
         that does not match."""
-        if table.num_clients == 0:
-            raise ValueError("moments about a point of no clients")
-        if table.num_clients > _native.POINT_MAX_CLIENTS:
-            raise NotImplementedError(
-                f"{table.num_clients} clients: moments about a point take at most {_native.POINT_MAX_CLIENTS}")
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("moments about a point read dense tensors: dequantise records first")
-        self._check_table(table, in_dtype)
-        n, T = table.num_clients, table.num_segments
-        p, _ = table.arrays()
-        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
-        if len(absent):
-            k, t = (int(x) for x in absent[0])
-            raise ValueError(f"client {k} lacks tensor {t}: moments compare whole updates")
+        self._refuse_before_table(table, in_dtype, "moments about a point", "", _native.POINT_MAX_CLIENTS)
+        p = self._whole_updates(table, in_dtype, "moments compare")
         if direction is None:
             raise ValueError("the direction is required")
-        tables = []
-        for what, tensors in (("centre", centre), ("direction", direction)):
-            if tensors is None:
-                tables.append(None)
-                continue
-            if len(tensors) != T:
-                raise ValueError(f"one {what} tensor per segment is required")
-            for t, (z, numel) in enumerate(zip(tensors, self.layout.numels)):
-                if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
-                    raise ValueError(
-                        f"{what} tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
-            tables.append((ctypes.c_void_p * T)(*[z.data_ptr() for z in tensors]))
+        vp = None if centre is None else self._segment_array("centre", centre)
+        gp = self._segment_array("direction", direction)
+        n = table.num_clients
         out = torch.empty((2, n), dtype=torch.float64, device=self.device)
         _native.check(
             self._lib.fedavg_moments_about_point(
-                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, tables[0], tables[1],
-                ctypes.c_void_p(out.data_ptr()), self.stream,
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, vp, gp, ctypes.c_void_p(out.data_ptr()),
+                self.stream,
             )
         )
         return out[0], out[1]
@@ -1061,41 +908,13 @@ class FedAvgContext:
         more than 1024 clients, an absent entry, quantised records, a non-finite coefficient, a
         divisor that is not finite and > 0, a point or an output that does not match, an output
         that is its point."""
-        if table.num_clients == 0:
-            raise ValueError("the fold about a point of no clients")
-        if table.num_clients > _native.POINT_MAX_CLIENTS:
-            raise NotImplementedError(
-                f"{table.num_clients} clients: the fold about a point takes at most {_native.POINT_MAX_CLIENTS}")
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("the fold about a point reads dense tensors: dequantise records first")
+        self._refuse_before_table(table, in_dtype, "the fold about a point", "s", _native.POINT_MAX_CLIENTS)
         ocode = out_code(out_dtype)
-        self._check_table(table, in_dtype)
-        n, T = table.num_clients, table.num_segments
-        p, _ = table.arrays()
-        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
-        if len(absent):
-            k, t = (int(x) for x in absent[0])
-            raise ValueError(f"client {k} lacks tensor {t}: the fold about a point takes whole updates")
-        coef = np.ascontiguousarray([float(c) for c in coefficients], dtype=np.float64)
-        if coef.shape != (n,):
-            raise ValueError(f"one coefficient per client is required: {coef.size} for {n} clients")
-        if not np.isfinite(coef).all():
-            raise ValueError("the coefficients must be finite")
-        divisor = float(divisor)
-        if not (divisor > 0 and math.isfinite(divisor)):
-            raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
-        if len(point) != T or len(outs) != T:
-            raise ValueError("one point tensor and one output tensor per segment are required")
-        for t, (z, o, numel) in enumerate(zip(point, outs, self.layout.numels)):
-            if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
-                raise ValueError(f"point tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
-            if o.dtype != out_dtype or o.device != self.device or o.numel() != numel or not o.is_contiguous():
-                raise ValueError(
-                    f"output tensor {t}: contiguous {out_dtype} of {numel} elements on {self.device} is required")
-            if o.data_ptr() == z.data_ptr():
-                raise ValueError(f"output tensor {t} is its point: the step is not in-place, ping-pong two buffers")
-        zp = (ctypes.c_void_p * T)(*[z.data_ptr() for z in point])
-        op = (ctypes.c_void_p * T)(*[o.data_ptr() for o in outs])
+        p = self._whole_updates(table, in_dtype, "the fold about a point takes")
+        n = table.num_clients
+        coef = _client_scalars(coefficients, n, "coefficient")
+        divisor = _divisor(divisor)
+        zp, op = self._source_and_outputs("point", point, outs, out_dtype, NOT_IN_PLACE)
         _native.check(
             self._lib.fedavg_fold_about_point(
                 self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), coef.ctypes.data_as(_DBL), n, divisor, zp, op,
@@ -1123,32 +942,14 @@ class FedAvgContext:
         Refused before any launch: no clients, more than 1024, a delta that does not match its
         segment, mixed value dtypes, a non-finite weight, a divisor that is not finite and > 0, a
         base or an output that does not match, an output that is its base."""
-        T = self.layout.num_segments
         ocode = out_code(out_dtype)
         table = rows if isinstance(rows, SparseTable) else SparseTable(rows, self.layout, self.device)
         if table.layout != self.layout or table.device != self.device:
             raise ValueError("the sparse table was built for another layout or device")
         n, iptr, vptr, nnz, vcode = table.num_clients, table.iptr, table.vptr, table.nnz, dtype_code(table.dtype)
-        w = np.ascontiguousarray([float(x) for x in weights], dtype=np.float64)
-        if w.shape != (n,):
-            raise ValueError(f"one weight per client is required: {w.size} for {n} clients")
-        if not np.isfinite(w).all():
-            raise ValueError("the weights must be finite")
-        divisor = float(divisor)
-        if not (divisor > 0 and math.isfinite(divisor)):
-            raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
-        if len(base) != T or len(outs) != T:
-            raise ValueError("one base tensor and one output tensor per segment are required")
-        for t, (z, o, numel) in enumerate(zip(base, outs, self.layout.numels)):
-            if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
-                raise ValueError(f"base tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
-            if o.dtype != out_dtype or o.device != self.device or o.numel() != numel or not o.is_contiguous():
-                raise ValueError(
-                    f"output tensor {t}: contiguous {out_dtype} of {numel} elements on {self.device} is required")
-            if o.data_ptr() == z.data_ptr():
-                raise ValueError(f"output tensor {t} is its base: the sparse fold is not in-place")
-        zp = (ctypes.c_void_p * T)(*[z.data_ptr() for z in base])
-        op = (ctypes.c_void_p * T)(*[o.data_ptr() for o in outs])
+        w = _client_scalars(weights, n, "weight")
+        divisor = _divisor(divisor)
+        zp, op = self._source_and_outputs("base", base, outs, out_dtype, "the sparse fold is not in-place")
         _native.check(
             self._lib.fedavg_sparse_aggregate_delta(
                 self._h, iptr.ctypes.data_as(_PTR), vptr.ctypes.data_as(_PTR),
@@ -1172,30 +973,19 @@ class FedAvgContext:
         ``raise_on_nan`` turns into ``NaNAggregationError``."""
         if codec not in _native.RECORD_CODES:
             raise ValueError(f"codec {codec} is not a record format")
-        f64 = codec in (_native.QSGD_F64, _native.NNADQ_F64)
-        nnadq = codec in (_native.NNADQ_F32, _native.NNADQ_F64)
-        dt = torch.float64 if f64 else torch.float32
+        dt = torch.float64 if codec in (_native.QSGD_F64, _native.NNADQ_F64) else torch.float32
         T = len(tensors)
         if T == 0 or len(records) != T:
             raise ValueError("one record per tensor and at least one tensor are required")
-        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
-            raise ValueError("the seed is a uint64 and the draw a uint32")
-        ids = np.arange(T, dtype=np.uint32) if tensor_ids is None else np.ascontiguousarray(tensor_ids, dtype=np.uint32)
-        if ids.shape != (T,):
-            raise ValueError("one stream id per tensor is required")
-        iptr = np.zeros(T, dtype=np.uint64)
-        rptr = np.zeros(T, dtype=np.uint64)
-        numels = np.zeros(T, dtype=np.int64)
-        for t, (x, r) in enumerate(zip(tensors, records)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"tensor {t}: a contiguous {dt} tensor on {self.device} is required")
-            n = x.numel()
-            need = 32 + (n + 15) // 16 * 16 if nnadq else 16 + (n + 15) // 16 * 16 + ((n + 7) // 8 + 15) // 16 * 16
-            if r.dtype != torch.uint8 or r.device != self.device or not r.is_contiguous() or r.numel() != need:
-                raise ValueError(f"record {t}: a contiguous uint8 tensor of {need} bytes on {self.device} is required")
-            iptr[t] = x.data_ptr() if n else 0
-            rptr[t] = r.data_ptr()
-            numels[t] = n
+        ids = _stream_ids(seed, draw, tensor_ids, T)
+        numels = [x.numel() for x in tensors]
+        needs = [_native.record_bytes(codec, n) for n in numels]
+        t, fault = _first(T, self._first_unfit(tensors, dt), self._first_unfit(records, torch.uint8, needs))
+        if fault == 0:
+            raise self._flat_refusal("tensor", t, dt)
+        if fault == 1:
+            raise self._record_refusal(t, needs[t])
+        iptr, rptr, numels = _addresses(tensors, numels), _addresses(records, needs), np.array(numels, dtype=np.int64)
         _native.check(
             self._lib.fedavg_quant_encode(
                 self._h, codec, iptr.ctypes.data, numels.ctypes.data, ids.ctypes.data, T, rptr.ctypes.data,
@@ -1217,34 +1007,29 @@ class FedAvgContext:
         if codec not in _native.RECORD_CODES:
             raise ValueError(f"codec {codec} is not a record format")
         f64 = codec in (_native.QSGD_F64, _native.NNADQ_F64)
-        nnadq = codec in (_native.NNADQ_F32, _native.NNADQ_F64)
         dt = torch.float64 if f64 else torch.float32
         T = len(records)
         if T == 0 or len(outs) != T or (outs64 is not None and len(outs64) != T):
             raise ValueError("one output per record and at least one record are required")
         if outs64 is not None and f64:
             raise ValueError("the fp64 copy is offered for the fp32 codecs: an fp64 codec's output is fp64")
-        ptrs = np.zeros((3, T), dtype=np.uint64)  # record, output, fp64 output
-        numels = np.zeros(T, dtype=np.int64)
-        for t, (r, o) in enumerate(zip(records, outs)):
-            if o.dtype != dt or o.device != self.device or not o.is_contiguous():
-                raise ValueError(f"output {t}: a contiguous {dt} tensor on {self.device} is required")
-            n = o.numel()
-            need = 32 + (n + 15) // 16 * 16 if nnadq else 16 + (n + 15) // 16 * 16 + ((n + 7) // 8 + 15) // 16 * 16
-            if r.dtype != torch.uint8 or r.device != self.device or not r.is_contiguous() or r.numel() != need:
-                raise ValueError(f"record {t}: a contiguous uint8 tensor of {need} bytes on {self.device} is required")
-            ptrs[0, t], ptrs[1, t] = r.data_ptr(), o.data_ptr() if n else 0
-            if outs64 is not None:
-                w = outs64[t]
-                if w.dtype != torch.float64 or w.device != self.device or not w.is_contiguous() or w.numel() != n:
-                    raise ValueError(f"fp64 output {t}: a contiguous torch.float64 tensor of {n} elements on "
-                                     f"{self.device} is required")
-                ptrs[2, t] = w.data_ptr() if n else 0
-            numels[t] = n
+        numels = [o.numel() for o in outs]
+        needs = [_native.record_bytes(codec, n) for n in numels]
+        t, fault = _first(T, self._first_unfit(outs, dt), self._first_unfit(records, torch.uint8, needs),
+                          T if outs64 is None else self._first_unfit(outs64, torch.float64, numels))
+        if fault == 0:
+            raise self._flat_refusal("output", t, dt)
+        if fault == 1:
+            raise self._record_refusal(t, needs[t])
+        if fault == 2:
+            raise self._flat_refusal("fp64 output", t, torch.float64, numels[t])
+        rptr, optr = _addresses(records, needs), _addresses(outs, numels)
+        wptr = None if outs64 is None else _addresses(outs64, numels)
+        numels = np.array(numels, dtype=np.int64)
         _native.check(
             self._lib.fedavg_quant_decode(
-                self._h, codec, ptrs[0].ctypes.data, numels.ctypes.data, T, ptrs[1].ctypes.data,
-                ptrs[2].ctypes.data if outs64 is not None else None, self.stream,
+                self._h, codec, rptr.ctypes.data, numels.ctypes.data, T, optr.ctypes.data,
+                None if wptr is None else wptr.ctypes.data, self.stream,
             )
         )
 
@@ -1261,27 +1046,17 @@ class FedAvgContext:
         T = len(tensors)
         if T == 0 or len(outs) != T:
             raise ValueError("one output per tensor and at least one tensor are required")
-        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
-            raise ValueError("the seed is a uint64 and the draw a uint32")
-        ids = np.arange(T, dtype=np.uint32) if tensor_ids is None else np.ascontiguousarray(tensor_ids, dtype=np.uint32)
-        if ids.shape != (T,):
-            raise ValueError("one stream id per tensor is required")
+        ids = _stream_ids(seed, draw, tensor_ids, T)
         dt = tensors[0].dtype
         if dt not in DTYPE_CODES:
             raise TypeError(f"the clip-and-noise pass takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
-        iptr = np.zeros(T, dtype=np.uint64)
-        optr = np.zeros(T, dtype=np.uint64)
-        numels = np.zeros(T, dtype=np.int64)
-        for t, (x, o) in enumerate(zip(tensors, outs)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"tensor {t}: a contiguous {dt} tensor on {self.device} is required")
-            if o.dtype != dt or o.device != self.device or not o.is_contiguous() or o.numel() != x.numel():
-                raise ValueError(f"output {t}: a contiguous {dt} tensor of {x.numel()} elements on {self.device} "
-                                 "is required")
-            n = x.numel()
-            iptr[t] = x.data_ptr() if n else 0
-            optr[t] = o.data_ptr() if n else 0
-            numels[t] = n
+        numels = [x.numel() for x in tensors]
+        t, fault = _first(T, self._first_unfit(tensors, dt), self._first_unfit(outs, dt, numels))
+        if fault == 0:
+            raise self._flat_refusal("tensor", t, dt)
+        if fault == 1:
+            raise self._flat_refusal("output", t, dt, numels[t])
+        iptr, optr, numels = _addresses(tensors, numels), _addresses(outs, numels), np.array(numels, dtype=np.int64)
         _native.check(
             self._lib.fedavg_dp_noise(
                 self._h, DTYPE_CODES[dt], iptr.ctypes.data, numels.ctypes.data, ids.ctypes.data, T, optr.ctypes.data,
@@ -1307,30 +1082,27 @@ class FedAvgContext:
         dt = deltas[0].dtype
         if dt not in DTYPE_CODES:
             raise TypeError(f"the top-k step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
-        ptrs = np.zeros((5, T), dtype=np.uint64)  # delta, error, index, value, residual
-        counts = np.zeros((2, T), dtype=np.int64)  # numel, keep
-        for t in range(T):
-            x, n, k = deltas[t], deltas[t].numel(), int(keeps[t])
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"delta {t}: a contiguous {dt} tensor on {self.device} is required")
-            if not 0 <= k <= n:
-                raise ValueError(f"delta {t}: keeps {k} of {n} elements")
-            e = None if errors is None else errors[t]
-            for what, y, dty, size in (("error", e, dt, n), ("index", indices[t], torch.int32, k),
-                                       ("value", values[t], dt, k), ("residual", residuals[t], dt, n)):
-                if y is not None and (y.dtype != dty or y.device != self.device or not y.is_contiguous()
-                                      or y.numel() != size):
-                    raise ValueError(f"{what} {t}: a contiguous {dty} tensor of {size} elements on {self.device} "
-                                     "is required")
-            ptrs[:, t] = (x.data_ptr() if n else 0, e.data_ptr() if e is not None and n else 0,
-                          indices[t].data_ptr() if k else 0, values[t].data_ptr() if k else 0,
-                          residuals[t].data_ptr() if n else 0)
-            counts[:, t] = (n, k)
+        ns, ks = [x.numel() for x in deltas], [int(k) for k in keeps]
+        groups = (("error", errors or (), dt, ns), ("index", indices, torch.int32, ks), ("value", values, dt, ks),
+                  ("residual", residuals, dt, ns))
+        t, fault = _first(T, self._first_unfit(deltas, dt),
+                          next((t for t, (k, n) in enumerate(zip(ks, ns)) if not 0 <= k <= n), T),
+                          *[self._first_unfit(g, dty, sizes) if g else T for _, g, dty, sizes in groups])
+        if fault == 0:
+            raise self._flat_refusal("delta", t, dt)
+        if fault == 1:
+            raise ValueError(f"delta {t}: keeps {ks[t]} of {ns[t]} elements")
+        if fault >= 2:
+            what, _, dty, sizes = groups[fault - 2]
+            raise self._flat_refusal(what, t, dty, sizes[t])
+        xptr, iptr, vptr, rptr = (_addresses(deltas, ns), _addresses(indices, ks), _addresses(values, ks),
+                                  _addresses(residuals, ns))
+        eptr = None if errors is None else _addresses(errors, ns)
+        ns, ks = np.array(ns, dtype=np.int64), np.array(ks, dtype=np.int64)
         _native.check(
             self._lib.fedavg_topk_sparsify(
-                self._h, DTYPE_CODES[dt], ptrs[0].ctypes.data, ptrs[1].ctypes.data if errors is not None else None,
-                counts[0].ctypes.data, counts[1].ctypes.data, T, ptrs[2].ctypes.data, ptrs[3].ctypes.data,
-                ptrs[4].ctypes.data, self.stream,
+                self._h, DTYPE_CODES[dt], xptr.ctypes.data, None if eptr is None else eptr.ctypes.data,
+                ns.ctypes.data, ks.ctypes.data, T, iptr.ctypes.data, vptr.ctypes.data, rptr.ctypes.data, self.stream,
             )
         )
 
@@ -1359,30 +1131,13 @@ class FedAvgContext:
         point and no ``*_out`` is its ``*_in``; the caller swaps its buffers once ``flags()`` came back
         clean. Refused before any launch: what ``fold_about_point`` refuses, the hyper-parameters
         ``check_server_opt`` refuses, moments that do not match or alias."""
-        if table.num_clients == 0:
-            raise ValueError("the server optimiser step of no clients")
-        if table.num_clients > _native.POINT_MAX_CLIENTS:
-            raise NotImplementedError(
-                f"{table.num_clients} clients: the server optimiser step takes at most {_native.POINT_MAX_CLIENTS}")
-        if dtype_code(in_dtype) in _native.RECORD_CODES:
-            raise NotImplementedError("the server optimiser step reads dense tensors: dequantise records first")
+        self._refuse_before_table(table, in_dtype, "the server optimiser step", "s", _native.POINT_MAX_CLIENTS)
         ocode = out_code(out_dtype)
         code, lr, beta1, omb1, beta2, omb2, tau = check_server_opt(mode, lr, beta1, beta2, tau)
-        self._check_table(table, in_dtype)
+        p = self._whole_updates(table, in_dtype, "the server optimiser step takes")
         n, T = table.num_clients, table.num_segments
-        p, _ = table.arrays()
-        absent = np.argwhere(np.asarray(p)[: n * T].reshape(n, T) == 0)
-        if len(absent):
-            k, t = (int(x) for x in absent[0])
-            raise ValueError(f"client {k} lacks tensor {t}: the server optimiser step takes whole updates")
-        coef = np.ascontiguousarray([float(c) for c in coefficients], dtype=np.float64)
-        if coef.shape != (n,):
-            raise ValueError(f"one coefficient per client is required: {coef.size} for {n} clients")
-        if not np.isfinite(coef).all():
-            raise ValueError("the coefficients must be finite")
-        divisor = float(divisor)
-        if not (divisor > 0 and math.isfinite(divisor)):
-            raise ValueError(f"the divisor must be a finite number > 0, not {divisor}")
+        coef = _client_scalars(coefficients, n, "coefficient")
+        divisor = _divisor(divisor)
         adaptive = code != _native.OPT_AVGM
         groups = [("point", point), ("first-moment input", m_in), ("first-moment output", m_out)]
         if adaptive:
@@ -1391,26 +1146,20 @@ class FedAvgContext:
             groups += [("second-moment input", v_in), ("second-moment output", v_out)]
         if len(outs) != T or any(len(g) != T for _, g in groups):
             raise ValueError("one point, moment and output tensor per segment are required")
-        for what, tensors in groups:
-            for t, (z, numel) in enumerate(zip(tensors, self.layout.numels)):
-                if z.dtype != torch.float64 or z.device != self.device or z.numel() != numel or not z.is_contiguous():
-                    raise ValueError(
-                        f"{what} tensor {t}: contiguous fp64 of {numel} elements on {self.device} is required")
-        for t, (o, numel) in enumerate(zip(outs, self.layout.numels)):
-            if o.dtype != out_dtype or o.device != self.device or o.numel() != numel or not o.is_contiguous():
-                raise ValueError(
-                    f"output tensor {t}: contiguous {out_dtype} of {numel} elements on {self.device} is required")
-            if o.data_ptr() == point[t].data_ptr():
-                raise ValueError(f"output tensor {t} is its point: the step is not in-place, ping-pong two buffers")
-            if m_out[t].data_ptr() == m_in[t].data_ptr() or (adaptive and v_out[t].data_ptr() == v_in[t].data_ptr()):
-                raise ValueError(f"moment tensor {t}: the step is not in-place, ping-pong two buffers")
-        arrays = [(ctypes.c_void_p * T)(*[z.data_ptr() for z in g]) if g is not None else None
-                  for g in (point, m_in, v_in if adaptive else None, m_out, v_out if adaptive else None, outs)]
+        zp, mi, mo, vi, vo = [self._segment_array(what, g) for what, g in groups] + [None] * (5 - len(groups))
+        t, fault = _first(T, self._first_unfit(outs, out_dtype, self.layout.numels), _first_shared(point, outs),
+                          min(_first_shared(m_in, m_out), _first_shared(v_in, v_out) if adaptive else T))
+        if fault == 0:
+            raise self._segment_refusal("output", t, out_dtype)
+        if fault == 1:
+            raise ValueError(f"output tensor {t} is its point: {NOT_IN_PLACE}")
+        if fault == 2:
+            raise ValueError(f"moment tensor {t}: {NOT_IN_PLACE}")
+        op = _pointer_array(outs)
         _native.check(
             self._lib.fedavg_server_opt_step(
                 self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), coef.ctypes.data_as(_DBL), n, divisor,
-                arrays[0], arrays[1], arrays[2], arrays[3], arrays[4], code, lr, beta1, omb1, beta2, omb2, tau,
-                arrays[5], ocode, self.stream,
+                zp, mi, vi, mo, vo, code, lr, beta1, omb1, beta2, omb2, tau, op, ocode, self.stream,
             )
         )
 

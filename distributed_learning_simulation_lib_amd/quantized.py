@@ -71,9 +71,7 @@ class QuantizedDtype:
 
     def record_bytes(self, numel: int) -> int:
         """Byte size of one record of a numel-element tensor (== fedavg_<scheme>_record_bytes)."""
-        if self.scheme == "nnadq":
-            return NNADQ_HEADER_BYTES + _align16(numel)
-        return record_bytes(numel)
+        return _native.record_bytes(self.code, numel)
 
 
 QSGD_F32 = QuantizedDtype("qsgd_f32", torch.float32, _native.QSGD_F32)
@@ -95,7 +93,7 @@ def sign_offset(numel: int) -> int:
 
 def record_bytes(numel: int) -> int:
     """Byte size of one record (== fedavg_qsgd_record_bytes)."""
-    return sign_offset(numel) + _align16((numel + 7) // 8)
+    return _native.record_bytes(_native.QSGD_F32, numel)
 
 
 @dataclass
