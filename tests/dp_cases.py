@@ -27,12 +27,39 @@ def list_cases() -> dict[str, tuple[tuple[int, ...], float]]:
     cases[f"n{tl}_below"] = ((tl,), 1.0e4)  # the norm stays below C: s = 1
     cases["three"] = ((1, tl + 3, 5), C)    # the middle tensor is placed one element off 16 bytes
     cases["with_empty"] = ((7, 0, tl + 1), C)
+    # 302 pieces: the scale pass's lanes make a second trip, whose terms come from other tensors
+    cases["many"] = (tuple((1, 2, 3, 5, 8, 9)[i % 6] for i in range(300)) + (tl + 1,), C)
     return cases
+
+
+def list_offsets(name: str) -> list[int]:
+    """Elements past 16-byte alignment at which the GPU test places each tensor of a list case."""
+    n = len(list_cases()[name][0])
+    if name == "three":
+        return [0, 1, 0]
+    if name == "many":
+        return [1 if i % 3 == 0 else 0 for i in range(n)]
+    return [0] * n
 
 
 def row_cases() -> list[tuple[int, int]]:
     tl = ref.tile()
-    return [(1, 1), (3, 1), (5, 7), (4, 64), (300, 64), (2, tl + 1)]
+    # (9, 100) .. (5, 1000): teams of 32 .. 256 lanes for fp32, 16 .. 128 for the 16-bit types, 64 ..
+    # 256 for fp64 (row_team below), with dead teams in the last workgroup; (1500, 3): more partials
+    # and scales than the workspace's first 1024
+    return [(1, 1), (3, 1), (5, 7), (4, 64), (300, 64), (2, tl + 1), (9, 100), (7, 200), (7, 500), (5, 1000),
+            (1500, 3)]
+
+
+def row_team(length: int, dtype: str) -> int:
+    """The lanes that sum one piece of a row of ``length`` elements, as fedavg_dp_noise chooses them:
+    the power of two that covers the piece's 16-byte groups, at most a workgroup."""
+    tl, lanes, g = ref.tile(), ref.kernel_constant("dp_threads"), ref.group(dtype)
+    groups = -(-min(length, tl) // g)
+    team = 1
+    while team < lanes and team < groups:
+        team *= 2
+    return team
 
 
 def values(n: int, dtype: str, seed: int) -> torch.Tensor:

@@ -91,8 +91,7 @@ def _check(ctx, device, xs, offsets, want, row_len, c, ids, redraw_want):
 def test_whole_list_matches_restatement(ctx, hip_device, name, dtype):
     xs, c, want = cases.list_case(name, dtype)
     _, _, redraw = cases.list_case(name, dtype, cases.DRAW + 1)
-    offsets = [0, 1, 0] if name == "three" else [0] * len(xs)
-    _check(ctx, hip_device, xs, offsets, want, 0, c, None, redraw)
+    _check(ctx, hip_device, xs, cases.list_offsets(name), want, 0, c, None, redraw)
 
 
 @pytest.mark.parametrize("dtype", ref.DTYPES)
