@@ -23,6 +23,7 @@ from .algorithm import (
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
     ServerOptFedAVGAlgorithm,
+    SignFedAVGAlgorithm,
     SparseFedAVGAlgorithm,
 )
 from .algorithm_repository import AlgorithmRepository
@@ -53,6 +54,7 @@ from .quantized import (
     StochasticQuantClientEndpoint,
     philox_uniforms,
 )
+from .sign import SignDelta, SignEndpoint, SignErrorFeedback, sign_compress, sign_compress_parameter
 from .sparse import SparseDelta, TopKErrorFeedback, TopKSparseEndpoint, topk_sparsify, topk_sparsify_parameter
 
 __all__ = [
@@ -88,6 +90,10 @@ __all__ = [
     "QuantClientEndpoint",
     "RobustFedAVGAlgorithm",
     "ServerOptFedAVGAlgorithm",
+    "SignDelta",
+    "SignEndpoint",
+    "SignErrorFeedback",
+    "SignFedAVGAlgorithm",
     "SparseDelta",
     "SparseFedAVGAlgorithm",
     "StochasticQuantClientEndpoint",
@@ -99,6 +105,8 @@ __all__ = [
     "get_message_size",
     "normal_stream",
     "philox_uniforms",
+    "sign_compress",
+    "sign_compress_parameter",
     "topk_sparsify",
     "topk_sparsify_parameter",
 ]
@@ -238,6 +246,19 @@ def _register_builtin() -> None:
             client_endpoint_cls=TopKSparseEndpoint,
             algorithm_cls=SparseFedAVGAlgorithm,
         )
+    # FedAvg over 1-bit sign deltas, folded from the bits, and the same with workers that compress their
+    # diffs before sending (scaled sign with error feedback): the sign rule behind the sign endpoint
+    for name, endpoint in (("fed_avg_sign", {}), ("fed_avg_sign_ef", {"client_endpoint_cls": SignEndpoint})):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=SignFedAVGAlgorithm,
+                **endpoint,
+            )
     # FedAvg whose workers send their updates, and receive the broadcast, as QSGD or NNADQ records: the
     # plain server and rule (which folds records as they are) behind the quantised client endpoints. The
     # NNADQ weight has no default: the caller binds it through the endpoint's keyword arguments

@@ -12,10 +12,11 @@ from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 from .server_opt_algorithm import ServerOptFedAVGAlgorithm
+from .sign_fed_avg_algorithm import SignFedAVGAlgorithm
 from .sparse_fed_avg_algorithm import SparseFedAVGAlgorithm
 
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "CompositeAggregationAlgorithm",
            "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
            "PersonalizedFedAVGAlgorithm",
-           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SparseFedAVGAlgorithm"]
+           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SparseFedAVGAlgorithm"]

@@ -131,6 +131,66 @@ __device__ __forceinline__ void raise_flag(uint32_t* flag, int word) {
   __hip_atomic_store(flag + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The pinned sum of fedavg_dp_noise (include/fedavg_hip.h, "The order of the sum"), which
+// fedavg_sign_compress shares: its geometry, the one rounding of an fp64 value into a tensor's dtype
+// and the adjacent-pair tree.
+constexpr int kDThreads = 256;   // lanes per workgroup
+constexpr int kDTile = 4096;     // elements per piece of a sum and per tile of the apply pass
+
+// The float nearest to o that is odd where o is no float ("round to odd"): rounding it to a
+// narrower format (at most 22 bits) gives what one rounding of o gives.
+__device__ __forceinline__ uint32_t dp_odd_float_bits(double o) {
+  const float f = static_cast<float>(o);
+  uint32_t u = __float_as_uint(f);
+  if (o == o && static_cast<double>(f) != o) {
+    if (__builtin_fabs(static_cast<double>(f)) > __builtin_fabs(o)) u -= 1u;  // towards zero (from infinity too)
+    u |= 1u;
+  }
+  return u;
+}
+
+// RNE(o) into T, as the bits of element i of the image
+template <typename T>
+__device__ __forceinline__ void dp_put(u32x4& raw, int i, double o);
+template <>
+__device__ __forceinline__ void dp_put<float>(u32x4& raw, int i, double o) {
+  raw[i] = __float_as_uint(static_cast<float>(o));
+}
+template <>
+__device__ __forceinline__ void dp_put<double>(u32x4& raw, int i, double o) {
+  const uint64_t b = static_cast<uint64_t>(__double_as_longlong(o));
+  raw[2 * i] = static_cast<uint32_t>(b);
+  raw[2 * i + 1] = static_cast<uint32_t>(b >> 32);
+}
+template <>
+__device__ __forceinline__ void dp_put<__half>(u32x4& raw, int i, double o) {
+  const __half h = __float2half_rn(__uint_as_float(dp_odd_float_bits(o)));
+  raw[i / 2] |= static_cast<uint32_t>(__half_as_ushort(h)) << (16 * (i % 2));
+}
+template <>
+__device__ __forceinline__ void dp_put<bf16_t>(u32x4& raw, int i, double o) {
+  const uint32_t u = dp_odd_float_bits(o);
+  const uint32_t b = (o == o) ? (u + 0x7fffu + ((u >> 16) & 1u)) >> 16 : 0x7fc0u;
+  raw[i / 2] |= b << (16 * (i % 2));
+}
+
+// the adjacent-pair tree over the first `width` (a power of two) lanes of every aligned block of
+// `width` lanes; the block's sum is valid in its first lane
+__device__ __forceinline__ double dp_tree(double v, int width, double* sm) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    if (off < width) v = v + __shfl_xor(v, off);
+  }
+  if (width > 64) {  // the same for every lane of the workgroup
+    const int t = static_cast<int>(threadIdx.x);
+    if ((t & 63) == 0) sm[t >> 6] = v;
+    __syncthreads();
+    const double a = sm[0] + sm[1], b = sm[2] + sm[3];
+    v = width == 128 ? ((t & 128) ? b : a) : a + b;
+  }
+  return v;
+}
+
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): the block of counter (c0, c1, c2, c3) under key
 // (k0, k1). The streams of the broadcast encoder and of the clip-and-noise pass are cut from it.
 struct QWords {

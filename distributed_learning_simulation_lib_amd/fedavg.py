@@ -36,6 +36,7 @@ from .rules import (  # noqa: F401 - re-exported: ``from ...fedavg import krum_s
     ROBUST_MODES, SERVER_OPT_MODES, _sqrt_rn, bulyan_select, check_robust_rule, check_server_opt,
     clipping_coefficients, geometric_median_step, krum_select, robust_trim, server_opt_update, trust_coefficients,
 )
+from .sign import SignDelta, bit_bytes
 from .sparse import SparseDelta
 
 DTYPE_CODES: dict[torch.dtype, int] = {
@@ -398,6 +399,38 @@ class SparseTable:
         if len(dtypes) != 1:
             raise ValueError(f"the sparse deltas of one call share one value dtype, not {sorted(map(str, dtypes))}")
         self.dtype = dtypes.pop()
+        self.num_clients = n
+        self.layout = layout
+        self.device = device
+        self._keep = [list(row) for row in rows]
+
+
+class SignTable:
+    """Rows of sign deltas as the C-ABI arrays of ``fedavg_sign_aggregate_delta``: ``rows[i][t]`` is
+    client ``i``'s ``SignDelta`` of segment ``t`` of ``layout`` on ``device``, all of one scale dtype
+    (built once, reusable across calls; it keeps the tensors alive)."""
+
+    def __init__(self, rows: Sequence[Sequence[SignDelta]], layout: ModelLayout, device: torch.device) -> None:
+        n, T = len(rows), layout.num_segments
+        dtypes = set()
+        self.bptr = np.zeros(n * T, dtype=np.uint64)
+        self.sptr = np.zeros(n * T, dtype=np.uint64)
+        for i, row in enumerate(rows):
+            if len(row) != T:
+                raise ValueError(f"client {i}: one sign delta per segment is required")
+            for t, (d, numel) in enumerate(zip(row, layout.numels)):
+                if not isinstance(d, SignDelta):
+                    raise TypeError(f"client {i}, tensor {t}: a SignDelta is required, not {type(d).__name__}")
+                if d.numel != numel or d.bits.device != device or d.scale.device != device \
+                        or not d.bits.is_contiguous():
+                    raise ValueError(f"client {i}, tensor {t}: a contiguous sign delta of {numel} elements on "
+                                     f"{device} is required")
+                dtypes.add(d.scale.dtype)
+                self.bptr[i * T + t] = d.bits.data_ptr()
+                self.sptr[i * T + t] = d.scale.data_ptr()
+        if len(dtypes) > 1:
+            raise ValueError(f"the sign deltas of one call share one scale dtype, not {sorted(map(str, dtypes))}")
+        self.dtype = dtypes.pop() if dtypes else torch.float32
         self.num_clients = n
         self.layout = layout
         self.device = device
@@ -1103,6 +1136,80 @@ class FedAvgContext:
             self._lib.fedavg_topk_sparsify(
                 self._h, DTYPE_CODES[dt], xptr.ctypes.data, None if eptr is None else eptr.ctypes.data,
                 ns.ctypes.data, ks.ctypes.data, T, iptr.ctypes.data, vptr.ctypes.data, rptr.ctypes.data, self.stream,
+            )
+        )
+
+    def sign_compress(self, deltas: Sequence[torch.Tensor], errors: Sequence[torch.Tensor | None] | None,
+                      bits: Sequence[torch.Tensor], scales: Sequence[torch.Tensor],
+                      residuals: Sequence[torch.Tensor]) -> None:
+        """1-bit sign compression with error feedback of ``deltas`` (non-empty contiguous tensors of
+        one floating dtype on the context's device, of any sizes: the context's layout plays no
+        part) in three launches (``fedavg_sign_compress``): tensor ``t`` sends the
+        sign bits of ``deltas[t] + errors[t]`` (``errors`` or an entry of it may be ``None``: no
+        residual yet) as ``bits[t]`` (uint8, ``8 * ceil(numel / 64)`` bytes, 8-byte aligned) and their
+        mean magnitude as ``scales[t]`` (one element of the dtype), and leaves what it did not send
+        in ``residuals[t]``, which may be ``errors[t]`` or ``deltas[t]`` itself. Asynchronous; a
+        non-finite element latches the input flag (``flags()``)."""
+        T = len(deltas)
+        if T == 0 or not (len(bits) == len(scales) == len(residuals) == T) or (
+                errors is not None and len(errors) != T):
+            raise ValueError("one bit, scale and residual tensor per delta and at least one delta are required")
+        dt = deltas[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the sign step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        ns = [x.numel() for x in deltas]
+        nb, ones = [bit_bytes(n) for n in ns], [1] * T
+        groups = (("error", errors or (), dt, ns), ("bit", bits, torch.uint8, nb), ("scale", scales, dt, ones),
+                  ("residual", residuals, dt, ns))
+        t, fault = _first(T, self._first_unfit(deltas, dt), next((t for t, n in enumerate(ns) if n == 0), T),
+                          *[self._first_unfit(g, dty, sizes) if g else T for _, g, dty, sizes in groups])
+        if fault == 0:
+            raise self._flat_refusal("delta", t, dt)
+        if fault == 1:
+            raise ValueError(f"delta {t}: an empty tensor has scale +0.0 and no bits, and is the caller's")
+        if fault >= 2:
+            what, _, dty, sizes = groups[fault - 2]
+            raise self._flat_refusal(what, t, dty, sizes[t])
+        xptr, bptr, sptr, rptr = (_addresses(deltas, ns), _addresses(bits, nb), _addresses(scales, ones),
+                                  _addresses(residuals, ns))
+        eptr = None if errors is None else _addresses(errors, ns)
+        ns = np.array(ns, dtype=np.int64)
+        _native.check(
+            self._lib.fedavg_sign_compress(
+                self._h, DTYPE_CODES[dt], xptr.ctypes.data, None if eptr is None else eptr.ctypes.data,
+                ns.ctypes.data, T, bptr.ctypes.data, sptr.ctypes.data, rptr.ctypes.data, self.stream,
+            )
+        )
+
+    def sign_aggregate_delta(self, rows: Sequence[Sequence[SignDelta]] | SignTable, weights: Sequence[float],
+                             divisor: float, base: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                             out_dtype: torch.dtype = torch.float64) -> None:
+        """FedAvg of sign deltas against ``base`` in one launch (``fedavg_sign_aggregate_delta``,
+        DESIGN.md §5w): ``outs[t][e] = (sum_i (base[t][e] + d_i[e]) * w_i) / divisor`` with ``d_i[e]``
+        ``-scale_i`` where client ``i``'s bit of ``e`` is set and ``+scale_i`` elsewhere — bit for bit
+        the reference's ``restore()`` + ``FedAVGAlgorithm`` on the densified deltas, and
+        ``aggregate_delta`` on them. ``rows[i][t]`` is client ``i``'s ``SignDelta`` of segment ``t``
+        on the context's device, all of one scale dtype (or a ``SignTable`` built from such rows
+        once); the scales are read on the device. ``base`` is one contiguous fp64 tensor per segment,
+        ``outs`` one contiguous ``out_dtype`` tensor per segment, none of them its base's own
+        storage. The accumulator is not touched; the NaN flags are the caller's to read
+        (``raise_on_nan``). Refused before any launch: no clients, more than 1024, a delta that does
+        not match its segment, mixed scale dtypes, a bit buffer that is not 8-byte aligned, a
+        non-finite weight, a divisor that is not finite and > 0, a base or an output that does not
+        match, an output that is its base."""
+        ocode = out_code(out_dtype)
+        table = rows if isinstance(rows, SignTable) else SignTable(rows, self.layout, self.device)
+        if table.layout != self.layout or table.device != self.device:
+            raise ValueError("the sign table was built for another layout or device")
+        self._refuse_before_table(table, table.dtype, "the sign fold", "s", _native.POINT_MAX_CLIENTS)
+        n = table.num_clients
+        w = _client_scalars(weights, n, "weight")
+        divisor = _divisor(divisor)
+        zp, op = self._source_and_outputs("base", base, outs, out_dtype, "the sign fold is not in-place")
+        _native.check(
+            self._lib.fedavg_sign_aggregate_delta(
+                self._h, table.bptr.ctypes.data, table.sptr.ctypes.data, dtype_code(table.dtype),
+                w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
             )
         )
 

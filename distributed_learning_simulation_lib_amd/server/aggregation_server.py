@@ -35,6 +35,8 @@ from ..message import (
     wire_class,
 )
 from ..quantized import dequantize_parameter, is_quantized
+from ..sign import densify_parameter as densify_sign_parameter
+from ..sign import is_sign
 from ..sparse import densify_parameter, is_sparse
 
 
@@ -194,6 +196,11 @@ class AggregationServer:
         if is_delta_message(data) and is_sparse(data.delta_parameter):
             if not getattr(self._algorithm, "accepts_sparse_messages", False):
                 data.delta_parameter = densify_parameter(data.delta_parameter)
+        # the same for ``sign.SignDelta`` values (1-bit clients) and ``accepts_sign_messages``
+        # (SignFedAVGAlgorithm folds the bits themselves)
+        if is_delta_message(data) and is_sign(data.delta_parameter):
+            if not getattr(self._algorithm, "accepts_sign_messages", False):
+                data.delta_parameter = densify_sign_parameter(data.delta_parameter)
 
     def _aggregate_worker_data(self) -> Message:
         self._algorithm.set_old_parameter(self._model_cache.parameter)

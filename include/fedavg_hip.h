@@ -153,7 +153,10 @@ int32_t fedavg_build_flags(void);
  * fedavg_dp_noise;
  * "topk_tile" (elements per workgroup of the write pass: the unit of the per-tile counts),
  * "topk_chunk" (consecutive tiles per workgroup of the histogram and count passes) and
- * "topk_threads" of fedavg_topk_sparsify.
+ * "topk_threads" of fedavg_topk_sparsify;
+ * "sign_tile" (elements per workgroup), "sign_words" (64-bit words, and so elements per lane, of a
+ * wave), "sign_batch" (clients staged between two pairs of workgroup barriers: it does not enter the
+ * result) and "sign_threads" of fedavg_sign_aggregate_delta.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -896,6 +899,71 @@ int32_t fedavg_topk_sparsify(fedavg_ctx* ctx, int32_t dtype, const void* const* 
                              int32_t num_tensors, int32_t* const* index_ptrs /* [T], device */,
                              void* const* value_ptrs /* [T], device */, void* const* residual_ptrs /* [T], device */,
                              void* stream);
+
+/*
+ * 1-bit sign compression with error feedback (EF-signSGD; the `_sparsify` of the reference's
+ * worker/error_feedback_worker.py with the scaled sign as the scheme) on num_tensors device tensors of
+ * one dtype (FEDAVG_F32 / F16 / BF16 / F64) where they lie: what sign.sign_compress computes per
+ * tensor. The contract is DESIGN.md §5w; the oracle is the CPU path of sign.sign_compress.
+ *
+ * Tensor t holds numels[t] (host, 1 .. 2^31 - 1) elements at delta_ptrs[t], aligned to the element
+ * only. error_ptrs (NULL: no tensor has a residual yet) holds per tensor its residual of the same size
+ * and dtype, or NULL.
+ *   total[e] = delta[e] + error[e], the IEEE sum rounded once to nearest even into the dtype; without
+ *              an error total[e] is delta[e] bit for bit.
+ *   a[e]     = |total[e]| widened exactly to fp64; S = their fp64 sum in the order of fedavg_dp_noise's
+ *              row mode with the whole tensor as the one row ("The order of the sum" above: pieces of
+ *              "dp_tile" elements, groups of "dp_ae_<d>" elements, 256 lanes over the groups in
+ *              ascending order, the adjacent-pair tree, the lanes over the pieces, the tree again).
+ *   s64      = S / numels[t] (IEEE division); scale = s64 rounded to nearest even into the dtype,
+ *              stored at scale_ptrs[t] (one element of the dtype, aligned to it).
+ *   bit[e]   = the sign bit of total[e] (-0.0 has it set): bit e % 8 of byte e / 8 of bit_ptrs[t], an
+ *              8-byte aligned buffer of 8 * ceil(numel / 64) bytes; every byte of it is written and the
+ *              bits past numel in the last 64-bit word are 0.
+ *   sent[e]  = -scale where the bit is set, +scale elsewhere;
+ *   residual_ptrs[t][e] = total[e] - sent[e], rounded once to nearest even into the dtype.
+ * residual_ptrs[t] may be error_ptrs[t] or delta_ptrs[t] (every element is read and then written by
+ * the same lane in the last pass); no other overlap is allowed. Nothing outside the outputs is written.
+ *
+ * Three launches whatever num_tensors is (the piece partials, one scale per tensor, the bits and the
+ * residual); no atomics, no host round trip: asynchronous on `stream`. The result depends on the
+ * inputs alone. A non-finite total[e] latches FEDAVG_FLAG_INPUT_NAN (the outputs are then unspecified
+ * but stay inside their buffers). The accumulator and its state are not touched. A call's partials live
+ * in the context: calls on one context are ordered by their stream.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype; a NULL table other than error_ptrs;
+ * num_tensors < 1 or > 2^20; numels[t] < 1 or > 2^31 - 1; a NULL delta, residual, bit or scale buffer; a
+ * buffer not aligned to its element; a bit buffer not 8-byte aligned), FEDAVG_ERR_STATE (an open
+ * dynamic wave).
+ */
+int32_t fedavg_sign_compress(fedavg_ctx* ctx, int32_t dtype, const void* const* delta_ptrs /* [T], device */,
+                             const void* const* error_ptrs /* [T], device, or NULL; entries may be NULL */,
+                             const int64_t* numels /* [T], host */, int32_t num_tensors,
+                             void* const* bit_ptrs /* [T], device */, void* const* scale_ptrs /* [T], device */,
+                             void* const* residual_ptrs /* [T], device */, void* stream);
+
+/*
+ * FedAvg over sign deltas against the fp64 base (the cached global model) in one launch: per element e
+ * of segment t, with b = base_ptrs[t][e] and s_i the scalar at scale_ptrs[i * T + t] widened exactly,
+ *   d_i = (bit e of bit_ptrs[i * T + t]) ? -s_i : +s_i;  x_i = b + d_i;  p_i = x_i * w_i;
+ *   acc = p_0, then acc = acc + p_i in table order;  out[e] = acc / divisor
+ * each a separately rounded fp64 operation (no FMA, no leading 0 +; fp32 out: that result rounded to
+ * nearest even). Bit for bit the reference's restore() followed by FedAVGAlgorithm on the densified
+ * deltas, and fedavg_aggregate_delta on them. An element's result depends on its base, its bits, the
+ * scales and weights in table order and the divisor alone. bit_ptrs[i * T + t] is an 8-byte aligned
+ * buffer of 8 * ceil(numel_t / 64) bytes in the layout of fedavg_sign_compress; the bits past numel_t
+ * are ignored. All scales of a call share scale_dtype (FEDAVG_F32 / F16 / BF16 / F64); out_dtype is
+ * FEDAVG_F32 or FEDAVG_F64. Flags as the sparse fold: FEDAVG_FLAG_INPUT_NAN for a NaN x_i,
+ * FEDAVG_FLAG_ACC_NAN, FEDAVG_FLAG_RESULT_NAN. The accumulator is not touched. Asynchronous on `stream`.
+ * Refused before any launch: FEDAVG_ERR_INVALID (as fedavg_sparse_aggregate_delta: dtypes, NULL tables
+ * or entries, num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS, a non-finite weight, a divisor that is not
+ * finite and > 0, misaligned base / output / scale, out == base; and a bit buffer that is not 8-byte
+ * aligned), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_sign_aggregate_delta(fedavg_ctx* ctx, const void* const* bit_ptrs /* [n][T], device */,
+                                    const void* const* scale_ptrs /* [n][T], device */, int32_t scale_dtype,
+                                    const double* weights /* [n], host */, int32_t num_clients, double divisor,
+                                    const double* const* base_ptrs /* [T], device fp64 */,
+                                    void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
