@@ -24,6 +24,7 @@ from .algorithm import (
     RobustFedAVGAlgorithm,
     ServerOptFedAVGAlgorithm,
     SignFedAVGAlgorithm,
+    SignMajorityVoteAlgorithm,
     SparseFedAVGAlgorithm,
 )
 from .algorithm_repository import AlgorithmRepository
@@ -94,6 +95,7 @@ __all__ = [
     "SignEndpoint",
     "SignErrorFeedback",
     "SignFedAVGAlgorithm",
+    "SignMajorityVoteAlgorithm",
     "SparseDelta",
     "SparseFedAVGAlgorithm",
     "StochasticQuantClientEndpoint",
@@ -257,6 +259,20 @@ def _register_builtin() -> None:
                 client_cls=None,  # type: ignore[arg-type]
                 server_cls=AggregationServer,
                 algorithm_cls=SignFedAVGAlgorithm,
+                **endpoint,
+            )
+    # signSGD with majority vote over the same 1-bit deltas, and the same behind the sign endpoint: the
+    # step has no default, so the entry is the class itself and the caller binds it
+    # (functools.partial(entry, learning_rate=...))
+    for name, endpoint in (("fed_sign_majority", {}), ("fed_sign_majority_ef", {"client_endpoint_cls": SignEndpoint})):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=SignMajorityVoteAlgorithm,
                 **endpoint,
             )
     # FedAvg whose workers send their updates, and receive the broadcast, as QSGD or NNADQ records: the

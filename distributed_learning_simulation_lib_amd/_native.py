@@ -40,7 +40,8 @@ ROBUST_TRIMMED_MEAN, ROBUST_MEDIAN = 0, 1  # FEDAVG_ROBUST_*: fedavg_robust_aggr
 ROBUST_MAX_CLIENTS = 64
 KRUM_MAX_CLIENTS = 256  # FEDAVG_KRUM_MAX_CLIENTS: fedavg_pairwise_sqdist
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
-# fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta, fedavg_sign_aggregate_delta
+# fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta, fedavg_sign_aggregate_delta,
+# fedavg_sign_majority_vote
 ROUTE_MAX_SOURCES = 1024  # fedavg_route_rows
 ROUTE_MAX_NODE_SPACE = 1 << 28
 ROUTE_ERR_DUPLICATE, ROUTE_ERR_ORDER, ROUTE_ERR_RANGE = 1, 2, 4  # bits of fedavg_route_errors
@@ -174,6 +175,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fedavg_sign_aggregate_delta": (
         c_int32, [c_void_p, c_void_p, c_void_p, c_int32, _PD, c_int32, c_double, _PP, _PP, c_int32, c_void_p]),
+    # signSGD's majority vote over the same bits (sign_kernels.hip); the bit and mask tables as raw addresses
+    "fedavg_sign_majority_vote": (
+        c_int32, [c_void_p, c_void_p, c_int32, _PD, _PP, _PP, c_int32, c_void_p, c_void_p, c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

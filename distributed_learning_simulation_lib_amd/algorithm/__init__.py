@@ -13,10 +13,12 @@ from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 from .server_opt_algorithm import ServerOptFedAVGAlgorithm
 from .sign_fed_avg_algorithm import SignFedAVGAlgorithm
+from .sign_vote_algorithm import SignMajorityVoteAlgorithm
 from .sparse_fed_avg_algorithm import SparseFedAVGAlgorithm
 
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "CompositeAggregationAlgorithm",
            "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
            "PersonalizedFedAVGAlgorithm",
-           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SparseFedAVGAlgorithm"]
+           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
+           "SparseFedAVGAlgorithm"]

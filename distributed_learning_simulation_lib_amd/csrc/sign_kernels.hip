@@ -32,6 +32,19 @@
 // select and three fp64 operations: x = b + d, p = x * w, acc = acc + p. acc starts at -0.0, which
 // is the identity of the IEEE add for every p (signed zeros included), so the first product starts
 // the sum bit for bit. No atomics.
+//
+// The majority vote (signSGD with majority vote: Bernstein, Wang, Azizzadenesheli, Anandkumar, ICML
+// 2018; fedavg_sign_majority_vote) has no floating point until its last step. A
+// workgroup is one wave and owns a tile of kVtTile elements = 64 words; lane l owns word l, that is
+// 64 consecutive elements, and keeps their 64 vote counts bit-sliced: plane p is a 64-bit register
+// pair that holds bit p of all 64 counts. A client's word is loaded by the lane that owns it (8 bytes
+// per lane, one contiguous 512-byte line per wave and client, kVtLoads clients in flight) and the
+// clients go into the planes kVtGroup at a time through a carry-save adder tree (Harley-Seal), so the
+// carry ripples through the upper planes once per group. A bit-serial comparator against n / 2 then
+// gives the lane's two masks (2c > n, 2c == n), which are the packed outputs as they stand. For the
+// dense model the masks change hands: word k goes from lane k into a scalar register pair and is the
+// wave's lane mask of the elements 64 k + l, so the base loads and the output stores are whole
+// coalesced wave accesses and one select takes b itself on a tie. No LDS, no barrier, no atomics.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -39,6 +52,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "call_tables.h"
 #include "device_common.h"
@@ -401,17 +415,172 @@ __global__ __launch_bounds__(kSgThreads) void sign_fold_kernel(SgArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// the majority vote: blockIdx.x = tile, one wave per tile
+// ---------------------------------------------------------------------------------------
+constexpr int kVtThreads = 64;              // one wave: lane l owns word l of the tile
+constexpr int kVtTile = kVtThreads * 64;    // elements per workgroup
+constexpr int kVtGroup = 8;                 // clients a carry-save tree takes before one ripple
+constexpr int kVtLoads = 16;                // clients whose words a lane has in flight
+constexpr int kVtApply = 8;                 // words whose base values a lane has in flight
+// planes of the three cases: n < 2^planes, so the count fits and n / 2 < 2^(planes - 1)
+constexpr int kVtPlanesSmall = 3, kVtPlanesMid = 7, kVtPlanesAll = 11;
+static_assert(kVtLoads % kVtGroup == 0 && kVtThreads % kVtApply == 0, "whole groups, whole rounds");
+static_assert(kVtPlanesSmall >= 3, "the tree's ones, twos and fours are the planes 0, 1 and 2");
+static_assert((1 << kVtPlanesAll) > kSgMaxClients, "the top plane holds the count of every client");
+
+struct VtArgs {
+  const Span* tiles;
+  const uint64_t* const* bits;  // [n][num_segments]
+  const double* const* base;    // [num_segments]
+  void* const* outs;            // [num_segments]
+  uint64_t* const* neg;         // [num_segments], or NULL: not asked for
+  uint64_t* const* tie;         // [num_segments], or NULL
+  const double* steps;          // [num_segments]
+  uint32_t* flag;               // the context's NaN words (2: input)
+  int32_t num_segments;
+  int32_t n;
+};
+
+// a + b + c bit by bit: `lo` the sums, `hi` the carries
+__device__ __forceinline__ void vt_csa(uint64_t& hi, uint64_t& lo, uint64_t a, uint64_t b, uint64_t c) {
+  const uint64_t u = a ^ b;
+  hi = (a & b) | (u & c);
+  lo = u ^ c;
+}
+
+// The words w[G0 .. G0 + 8) of eight clients into the planes: seven carry-save adders leave the
+// planes 0, 1, 2 and one word of weight 8, which ripples through the planes from 3 up. A word of a
+// client past n is 0 and adds nothing. The carry out of the top plane is 0 because n < 2^P.
+template <int P, int G0>
+__device__ __forceinline__ void vt_add_group(uint64_t (&pl)[P], const uint64_t (&w)[kVtLoads]) {
+  uint64_t ones = pl[0], twos = pl[1], fours = pl[2];
+  uint64_t ta, tb, fa, fb, carry;
+  vt_csa(ta, ones, ones, w[G0 + 0], w[G0 + 1]);
+  vt_csa(tb, ones, ones, w[G0 + 2], w[G0 + 3]);
+  vt_csa(fa, twos, twos, ta, tb);
+  vt_csa(ta, ones, ones, w[G0 + 4], w[G0 + 5]);
+  vt_csa(tb, ones, ones, w[G0 + 6], w[G0 + 7]);
+  vt_csa(fb, twos, twos, ta, tb);
+  vt_csa(carry, fours, fours, fa, fb);
+  pl[0] = ones;
+  pl[1] = twos;
+  pl[2] = fours;
+#pragma unroll
+  for (int p = 3; p < P; ++p) {
+    const uint64_t t = pl[p] & carry;
+    pl[p] ^= carry;
+    carry = t;
+  }
+}
+
+// word `k` of the wave (held by lane k) as the lane mask of the elements 64 k + lane
+__device__ __forceinline__ bool vt_bit_of_word(uint32_t lo, uint32_t hi, int k) {
+  const uint32_t mlo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(lo), k));
+  const uint32_t mhi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hi), k));
+  return __builtin_amdgcn_inverse_ballot_w64((static_cast<uint64_t>(mhi) << 32) | mlo);
+}
+
+template <typename O, int P>
+__global__ __launch_bounds__(kVtThreads) void sign_vote_kernel(VtArgs a) {
+  const int lane = static_cast<int>(threadIdx.x);
+  const Span FEDAVG_AS_CONST* tp = (const Span FEDAVG_AS_CONST*)(a.tiles + blockIdx.x);
+  const int32_t seg = tp->seg, count = tp->count;
+  const int64_t start = tp->start;  // a multiple of kVtTile
+  const int n = a.n, T = a.num_segments;
+  const int nw = (count + 63) >> 6;  // words of the tile that exist: lanes past them load and store nothing
+  const int64_t word0 = start >> 6;
+  const bool mine = lane < nw;
+
+  // the counts of the lane's 64 elements, bit-sliced
+  uint64_t pl[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) pl[p] = 0ull;
+#pragma unroll 1
+  for (int c0 = 0; c0 < n; c0 += kVtLoads) {
+    uint64_t w[kVtLoads];
+#pragma unroll
+    for (int i = 0; i < kVtLoads; ++i) {  // all loads of the round before its first adder
+      w[i] = 0ull;
+      if (c0 + i < n) {  // the same for the whole wave
+        const uint64_t* const p = a.bits[static_cast<int64_t>(c0 + i) * T + seg] + word0;
+        if (mine) w[i] = ((const uint64_t FEDAVG_AS_GLOBAL*)p)[lane];
+      }
+    }
+    vt_add_group<P, 0>(pl, w);
+    if (c0 + kVtGroup < n) vt_add_group<P, kVtGroup>(pl, w);
+  }
+
+  // c > h and c == h with h = floor(n / 2), from the top plane down: 2c > n is c > h for either
+  // parity of n, 2c == n is c == h for an even n and never holds for an odd one
+  const uint32_t h = static_cast<uint32_t>(n) >> 1;
+  uint64_t gt = 0ull, eq = ~0ull;
+#pragma unroll
+  for (int p = P - 1; p >= 0; --p) {
+    const uint64_t hb = ((h >> p) & 1u) ? ~0ull : 0ull;  // in scalar registers
+    gt |= eq & pl[p] & ~hb;
+    eq &= ~(pl[p] ^ hb);
+  }
+  // the bits past the tensor's end (garbage in the clients' words) are cleared
+  const int left = count - lane * 64;
+  const uint64_t valid = left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
+  const uint64_t neg = gt & valid;
+  const uint64_t tie = (n & 1) ? 0ull : (eq & valid);
+  if (mine) {
+    if (a.neg != nullptr) ((uint64_t FEDAVG_AS_GLOBAL*)a.neg[seg])[word0 + lane] = neg;
+    if (a.tie != nullptr) ((uint64_t FEDAVG_AS_GLOBAL*)a.tie[seg])[word0 + lane] = tie;
+  }
+
+  // the dense model: word k's masks go to every lane, lane l takes element 64 k + l
+  const double s = a.steps[seg];
+  const double minus = -s;
+  const double FEDAVG_AS_GLOBAL* pb = (const double FEDAVG_AS_GLOBAL*)a.base[seg] + start;
+  O FEDAVG_AS_GLOBAL* po = (O FEDAVG_AS_GLOBAL*)a.outs[seg] + start;
+  const uint32_t nlo = static_cast<uint32_t>(neg), nhi = static_cast<uint32_t>(neg >> 32);
+  const uint32_t tlo = static_cast<uint32_t>(tie), thi = static_cast<uint32_t>(tie >> 32);
+  bool nan_in = false;
+  // A round is kVtApply words. kFull: every element of the round exists, so the round has no branch
+  // and its loads and stores are waited for one by one; the tensor's last round checks every element.
+  auto round = [&](int k0, auto full) {
+    constexpr bool kFull = decltype(full)::value;
+    double b[kVtApply];
+#pragma unroll
+    for (int u = 0; u < kVtApply; ++u) {  // all loads of the round before its first store
+      const int e = (k0 + u) * 64 + lane;
+      b[u] = (kFull || e < count) ? pb[e] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kVtApply; ++u) {  // k0 + u <= 63: a word past nw has empty masks
+      const int e = (k0 + u) * 64 + lane;
+      const bool is_neg = vt_bit_of_word(nlo, nhi, k0 + u);
+      const bool is_tie = vt_bit_of_word(tlo, thi, k0 + u);
+      nan_in |= b[u] != b[u];
+      const double r = b[u] + (is_neg ? minus : s);  // b + (-s) is b - s bit for bit
+      const double o = is_tie ? b[u] : r;            // a tie keeps b itself: -0.0 stays -0.0
+      if (kFull || e < count) po[e] = static_cast<O>(o);
+    }
+  };
+  int k0 = 0;
+#pragma unroll 1
+  for (; (k0 + kVtApply) * 64 <= count; k0 += kVtApply) round(k0, std::true_type{});
+  if (k0 < nw) round(k0, std::false_type{});  // fewer than kVtApply words are left
+  if (__ballot(nan_in) != 0ull && lane == 0) raise_flag(a.flag, 2);
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 struct SignState {
   Span* d_tiles = nullptr;  // the fold's tiles of the context's layout
   int64_t num_tiles = 0;
+  Span* d_vote_tiles = nullptr;  // the vote's
+  int64_t num_vote_tiles = 0;
   char* d_work = nullptr;   // the piece partials and the widened scales of the compress call in flight
   size_t work_cap = 0;
   TableRing ring;
   ~SignState() {
     ring.release();
     if (d_tiles) (void)hipFree(d_tiles);
+    if (d_vote_tiles) (void)hipFree(d_vote_tiles);
     if (d_work) (void)hipFree(d_work);
   }
 };
@@ -460,6 +629,12 @@ int32_t fedavg_internal_sign_constant(const char* name, int64_t* out) {
   else if (n == "sign_batch") *out = kSgBatch;
   else if (n == "sign_words") *out = kSgWords;
   else if (n == "sign_threads") *out = kSgThreads;
+  else if (n == "vote_tile") *out = kVtTile;
+  else if (n == "vote_threads") *out = kVtThreads;
+  else if (n == "vote_group") *out = kVtGroup;
+  else if (n == "vote_loads") *out = kVtLoads;
+  else if (n == "vote_small_clients") *out = (1 << kVtPlanesSmall) - 1;
+  else if (n == "vote_mid_clients") *out = (1 << kVtPlanesMid) - 1;
   else return FEDAVG_ERR_INVALID;
   return FEDAVG_OK;
 }
@@ -654,5 +829,110 @@ extern "C" int32_t fedavg_sign_aggregate_delta(fedavg_ctx* ctx, const void* cons
   if (e == hipSuccess) e = er;
   if (e != hipSuccess)
     return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("sign fold launch: ") + hipGetErrorString(e)).c_str());
+  return FEDAVG_OK;
+}
+
+namespace {
+
+template <typename O>
+void launch_vote(int n, unsigned tiles, hipStream_t s, const VtArgs& a) {
+  const dim3 grid(tiles), block(kVtThreads);
+  if (n < (1 << kVtPlanesSmall)) hipLaunchKernelGGL((sign_vote_kernel<O, kVtPlanesSmall>), grid, block, 0, s, a);
+  else if (n < (1 << kVtPlanesMid)) hipLaunchKernelGGL((sign_vote_kernel<O, kVtPlanesMid>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((sign_vote_kernel<O, kVtPlanesAll>), grid, block, 0, s, a);
+}
+
+}  // namespace
+
+extern "C" int32_t fedavg_sign_majority_vote(fedavg_ctx* ctx, const void* const* bit_ptrs, int32_t num_clients,
+                                             const double* steps, const double* const* base_ptrs,
+                                             void* const* out_ptrs, int32_t out_dtype, void* const* neg_ptrs,
+                                             void* const* tie_ptrs, void* stream) {
+  fedavg_robust_view v;
+  const int32_t rv = fedavg_internal_robust_view(ctx, &v);
+  if (rv != FEDAVG_OK) return rv;
+  void** slot = nullptr;
+  const int32_t rs = fedavg_internal_module_slot(ctx, FEDAVG_MODULE_SIGN, &slot);
+  if (rs != FEDAVG_OK) return rs;
+  if (v.busy) return fedavg_internal_fail(FEDAVG_ERR_STATE, "a dynamic wave is open on this context");
+  if (out_dtype != FEDAVG_F32 && out_dtype != FEDAVG_F64) return invalid("the sign vote writes fp32 or fp64");
+  if (bit_ptrs == nullptr || steps == nullptr || base_ptrs == nullptr || out_ptrs == nullptr)
+    return invalid("null bit table, steps, base or outputs");
+  if (num_clients < 1) return invalid("empty client table");
+  if (num_clients > kSgMaxClients)
+    return invalid(std::to_string(num_clients) + " clients: the sign vote takes at most " + std::to_string(kSgMaxClients));
+  const int T = v.num_segments;
+  const size_t out_bytes = out_dtype == FEDAVG_F64 ? 8 : 4;
+  const size_t entries = static_cast<size_t>(num_clients) * static_cast<size_t>(T);
+  for (size_t i = 0; i < entries; ++i) {
+    // the message is built only on a refusal: this loop runs n * T times on every call
+    const auto where = [T, i] { return "client " + std::to_string(i / T) + ", segment " + std::to_string(i % T); };
+    if (bit_ptrs[i] == nullptr) return invalid(where() + ": null bit buffer");
+    if (misaligned(bit_ptrs[i], 8)) return invalid(where() + ": the bit buffer is not 8-byte aligned");
+  }
+  for (int t = 0; t < T; ++t) {
+    const std::string who = "segment " + std::to_string(t);
+    if (!(std::isfinite(steps[t]) && steps[t] >= 0)) return invalid(who + ": the step must be finite and >= 0");
+    if (base_ptrs[t] == nullptr) return invalid("the base lacks segment " + std::to_string(t));
+    if (misaligned(base_ptrs[t], 8)) return invalid("base tensor not aligned to fp64");
+    if (out_ptrs[t] == nullptr) return invalid("null output pointer for segment " + std::to_string(t));
+    if (misaligned(out_ptrs[t], out_bytes)) return invalid("output tensor not aligned to its element size");
+    if (static_cast<const void*>(out_ptrs[t]) == static_cast<const void*>(base_ptrs[t]))
+      return invalid(who + ": the vote is not in-place (out == base)");
+    for (void* const* masks : {neg_ptrs, tie_ptrs}) {
+      if (masks == nullptr) continue;
+      if (masks[t] == nullptr) return invalid(who + ": null mask buffer");
+      if (misaligned(masks[t], 8)) return invalid(who + ": the mask buffer is not 8-byte aligned");
+    }
+  }
+
+  FEDAVG_TRY_HIP(hipSetDevice(v.device));
+  SignState* st = nullptr;
+  const int32_t re = ensure_state(slot, &st);
+  if (re != FEDAVG_OK) return re;
+  if (st->d_vote_tiles == nullptr)
+    FEDAVG_TRY(span_table(v.seg_numel, v.num_segments, kVtTile, "sign vote", "sign vote tile table", &st->d_vote_tiles,
+                          &st->num_vote_tiles));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+
+  // the call's tables: [n][T] bit pointers, then [T] each: base, output, neg mask, tie mask pointers
+  // (the masks' places stay empty where a table is not asked for), steps
+  const size_t ptr_bytes = sizeof(void*) * entries;
+  const size_t seg_bytes = sizeof(void*) * static_cast<size_t>(T);
+  const size_t o_base = ptr_bytes, o_out = o_base + seg_bytes, o_neg = o_out + seg_bytes, o_tie = o_neg + seg_bytes;
+  const size_t o_steps = o_tie + seg_bytes;
+  const size_t bytes = o_steps + sizeof(double) * static_cast<size_t>(T);
+  // `next` advances only once work that reads this slot has been enqueued and its event recorded
+  TableRing::Slot* slp = nullptr;
+  FEDAVG_TRY(st->ring.peek(bytes, &slp));
+  TableRing::Slot& sl = *slp;
+  std::memcpy(sl.host, bit_ptrs, ptr_bytes);
+  std::memcpy(sl.host + o_base, base_ptrs, seg_bytes);
+  std::memcpy(sl.host + o_out, out_ptrs, seg_bytes);
+  if (neg_ptrs != nullptr) std::memcpy(sl.host + o_neg, neg_ptrs, seg_bytes);
+  if (tie_ptrs != nullptr) std::memcpy(sl.host + o_tie, tie_ptrs, seg_bytes);
+  std::memcpy(sl.host + o_steps, steps, sizeof(double) * static_cast<size_t>(T));
+  FEDAVG_TRY(st->ring.submit(sl, bytes, s));
+
+  VtArgs a;
+  a.tiles = st->d_vote_tiles;
+  a.bits = reinterpret_cast<const uint64_t* const*>(sl.dev);
+  a.base = reinterpret_cast<const double* const*>(sl.dev + o_base);
+  a.outs = reinterpret_cast<void* const*>(sl.dev + o_out);
+  a.neg = neg_ptrs != nullptr ? reinterpret_cast<uint64_t* const*>(sl.dev + o_neg) : nullptr;
+  a.tie = tie_ptrs != nullptr ? reinterpret_cast<uint64_t* const*>(sl.dev + o_tie) : nullptr;
+  a.steps = reinterpret_cast<const double*>(sl.dev + o_steps);
+  a.flag = v.d_flag;
+  a.num_segments = T;
+  a.n = num_clients;
+  if (st->num_vote_tiles > 0) {
+    if (out_dtype == FEDAVG_F32) launch_vote<float>(num_clients, static_cast<unsigned>(st->num_vote_tiles), s, a);
+    else launch_vote<double>(num_clients, static_cast<unsigned>(st->num_vote_tiles), s, a);
+  }
+  hipError_t e = hipGetLastError();
+  const hipError_t er = st->ring.commit(sl, s);
+  if (e == hipSuccess) e = er;
+  if (e != hipSuccess)
+    return fedavg_internal_fail(FEDAVG_ERR_HIP, (std::string("sign vote launch: ") + hipGetErrorString(e)).c_str());
   return FEDAVG_OK;
 }

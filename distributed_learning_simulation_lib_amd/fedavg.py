@@ -411,10 +411,27 @@ class SignTable:
     (built once, reusable across calls; it keeps the tensors alive)."""
 
     def __init__(self, rows: Sequence[Sequence[SignDelta]], layout: ModelLayout, device: torch.device) -> None:
+        bits = SignBitTable(rows, layout, device)
+        dtypes = {d.scale.dtype for row in rows for d in row}
+        if len(dtypes) > 1:
+            raise ValueError(f"the sign deltas of one call share one scale dtype, not {sorted(map(str, dtypes))}")
+        self.bptr = bits.bptr
+        self.sptr = np.array([d.scale.data_ptr() for row in rows for d in row], dtype=np.uint64)
+        self.dtype = dtypes.pop() if dtypes else torch.float32
+        self.num_clients = bits.num_clients
+        self.layout = layout
+        self.device = device
+        self._keep = bits._keep
+
+
+class SignBitTable:
+    """The bit half of a ``SignTable``, for ``fedavg_sign_majority_vote``, which reads no scale:
+    ``rows[i][t]`` is client ``i``'s ``SignDelta`` of segment ``t`` of ``layout`` on ``device``, of any
+    scale dtypes (built once, reusable across calls; it keeps the tensors alive)."""
+
+    def __init__(self, rows: Sequence[Sequence[SignDelta]], layout: ModelLayout, device: torch.device) -> None:
         n, T = len(rows), layout.num_segments
-        dtypes = set()
         self.bptr = np.zeros(n * T, dtype=np.uint64)
-        self.sptr = np.zeros(n * T, dtype=np.uint64)
         for i, row in enumerate(rows):
             if len(row) != T:
                 raise ValueError(f"client {i}: one sign delta per segment is required")
@@ -425,12 +442,7 @@ class SignTable:
                         or not d.bits.is_contiguous():
                     raise ValueError(f"client {i}, tensor {t}: a contiguous sign delta of {numel} elements on "
                                      f"{device} is required")
-                dtypes.add(d.scale.dtype)
                 self.bptr[i * T + t] = d.bits.data_ptr()
-                self.sptr[i * T + t] = d.scale.data_ptr()
-        if len(dtypes) > 1:
-            raise ValueError(f"the sign deltas of one call share one scale dtype, not {sorted(map(str, dtypes))}")
-        self.dtype = dtypes.pop() if dtypes else torch.float32
         self.num_clients = n
         self.layout = layout
         self.device = device
@@ -1210,6 +1222,52 @@ class FedAvgContext:
             self._lib.fedavg_sign_aggregate_delta(
                 self._h, table.bptr.ctypes.data, table.sptr.ctypes.data, dtype_code(table.dtype),
                 w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
+            )
+        )
+
+    def sign_majority_vote(self, rows: Sequence[Sequence[SignDelta]] | SignTable | SignBitTable,
+                           steps: Sequence[float], base: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                           out_dtype: torch.dtype = torch.float64, neg_bits: Sequence[torch.Tensor] | None = None,
+                           tie_bits: Sequence[torch.Tensor] | None = None) -> None:
+        """signSGD's majority vote over sign deltas in one launch (``fedavg_sign_majority_vote``; not
+        a reference algorithm): with ``c`` the number of the ``n`` clients whose bit of
+        an element is set, ``outs[t][e]`` is ``base[t][e] - steps[t]`` where ``2c > n``, ``base[t][e] +
+        steps[t]`` where ``2c < n`` and ``base[t][e]`` bit for bit on a tie. The vote is unweighted and
+        reads no scale, so the rows may mix scale dtypes. ``rows[i][t]`` is client ``i``'s
+        ``SignDelta`` of segment ``t`` on the context's device (or a ``SignTable`` / ``SignBitTable``
+        built from such rows once); ``steps`` one finite float >= 0 per segment; ``base`` one
+        contiguous fp64 tensor per segment, ``outs`` one contiguous ``out_dtype`` tensor per segment,
+        none of them its base's own storage. ``neg_bits`` / ``tie_bits`` (optional) receive the packed
+        vote, one uint8 tensor of ``8 * ceil(numel / 64)`` bytes per segment, 8-byte aligned: bit ``e``
+        is set where ``2c > n`` / ``2c == n``, the padding bits are 0. The accumulator is not touched; a
+        NaN base latches the input flag, which is the caller's to read. Refused before any launch:
+        no clients, more than 1024, a delta that does not match its segment, a bit or mask buffer
+        that is not 8-byte aligned, a step that is not finite or is negative, a base, an output or a
+        mask that does not match, an output that is its base."""
+        ocode = out_code(out_dtype)
+        table = rows if isinstance(rows, (SignTable, SignBitTable)) else SignBitTable(rows, self.layout, self.device)
+        if table.layout != self.layout or table.device != self.device:
+            raise ValueError("the sign table was built for another layout or device")
+        self._refuse_before_table(table, torch.float64, "the sign vote", "s", _native.POINT_MAX_CLIENTS)
+        T = self.layout.num_segments
+        s = np.ascontiguousarray([float(x) for x in steps], dtype=np.float64)
+        if s.shape != (T,):
+            raise ValueError(f"one step per segment is required: {s.size} for {T} segments")
+        if not (np.isfinite(s).all() and (s >= 0).all()):
+            raise ValueError("the steps must be finite and >= 0")
+        zp, op = self._source_and_outputs("base", base, outs, out_dtype, "the sign vote is not in-place")
+        nb = [bit_bytes(n) for n in self.layout.numels]
+        masks = []
+        for what, group in (("negative mask", neg_bits), ("tie mask", tie_bits)):
+            if group is not None:
+                t = self._first_unfit(group, torch.uint8, nb) if len(group) == T else 0
+                if t < T:
+                    raise self._flat_refusal(what, t, torch.uint8, nb[t])
+            masks.append(None if group is None else _addresses(group, nb))
+        _native.check(
+            self._lib.fedavg_sign_majority_vote(
+                self._h, table.bptr.ctypes.data, table.num_clients, s.ctypes.data_as(_DBL), zp, op, ocode,
+                *(None if m is None else m.ctypes.data for m in masks), self.stream,
             )
         )
 

@@ -156,7 +156,12 @@ int32_t fedavg_build_flags(void);
  * "topk_threads" of fedavg_topk_sparsify;
  * "sign_tile" (elements per workgroup), "sign_words" (64-bit words, and so elements per lane, of a
  * wave), "sign_batch" (clients staged between two pairs of workgroup barriers: it does not enter the
- * result) and "sign_threads" of fedavg_sign_aggregate_delta.
+ * result) and "sign_threads" of fedavg_sign_aggregate_delta;
+ * "vote_tile" (elements per workgroup: one wave, one 64-bit word per lane), "vote_threads",
+ * "vote_group" (clients one carry-save tree takes before its carry ripples), "vote_loads" (clients
+ * whose words a lane has in flight), "vote_small_clients" and "vote_mid_clients" (the largest client
+ * counts of the kernel's 3-plane and 7-plane cases; above them it keeps 11 planes) of
+ * fedavg_sign_majority_vote: none of them enters the result.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -964,6 +969,37 @@ int32_t fedavg_sign_aggregate_delta(fedavg_ctx* ctx, const void* const* bit_ptrs
                                     const double* weights /* [n], host */, int32_t num_clients, double divisor,
                                     const double* const* base_ptrs /* [T], device fp64 */,
                                     void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
+
+/*
+ * signSGD with majority vote (Bernstein, Wang, Azizzadenesheli, Anandkumar, ICML 2018) over sign
+ * deltas, in one launch for the whole layout: per coordinate the server takes the sign that most
+ * clients sent and steps the fp64 base (the cached global model) by a fixed amount in that direction.
+ * Not a reference algorithm: the contract is DESIGN.md §5x and parity is bit-identity with a plain
+ * restatement of these lines. Per element e of segment t:
+ *   c = the number of clients i < num_clients whose bit e of bit_ptrs[i * T + t] is set (a set bit is
+ *       a negative vote); the clients are unweighted and their order plays no part; scales are not read;
+ *   b = base_ptrs[t][e];  s = steps[t] (host, finite, >= 0);
+ *   2c > n:  out = b - s (one fp64 subtraction);   2c < n:  out = b + s (one fp64 addition);
+ *   2c == n (a tie): out = b bit for bit (-0.0 stays -0.0: there is no b + 0.0).
+ * fp32 out is that value rounded to nearest even. bit_ptrs[i * T + t] is an 8-byte aligned buffer of
+ * 8 * ceil(numel_t / 64) bytes in the layout of fedavg_sign_compress; the bits past numel_t are ignored.
+ * neg_ptrs / tie_ptrs (either may be NULL) receive the packed vote for a 1-bit downlink: bit e of
+ * neg_ptrs[t] is set where 2c > n, bit e of tie_ptrs[t] where 2c == n; each is an 8-byte aligned buffer of
+ * 8 * ceil(numel_t / 64) bytes, every byte of which is written, the bits past numel_t as 0.
+ * An element's result depends on its base, its n bits, n and steps[t] alone. A NaN b latches
+ * FEDAVG_FLAG_INPUT_NAN and no other flag can be raised (s is finite; +inf / -inf bases pass through).
+ * The accumulator and its state are not touched. No atomics. Asynchronous on `stream`.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a NULL table or entry other than the two mask tables;
+ * num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS; a step that is not finite or is negative; a bit or
+ * mask buffer that is not 8-byte aligned; a misaligned base or output; out == base; a bad out_dtype),
+ * FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_sign_majority_vote(fedavg_ctx* ctx, const void* const* bit_ptrs /* [n][T], device */,
+                                  int32_t num_clients, const double* steps /* [T], host */,
+                                  const double* const* base_ptrs /* [T], device fp64 */,
+                                  void* const* out_ptrs /* [T], device */, int32_t out_dtype,
+                                  void* const* neg_ptrs /* [T] device, or NULL */,
+                                  void* const* tie_ptrs /* [T] device, or NULL */, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
