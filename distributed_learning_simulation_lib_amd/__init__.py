@@ -15,6 +15,7 @@ from .algorithm import (
     CompositeAggregationAlgorithm,
     FedAVGAlgorithm,
     FLTrustFedAVGAlgorithm,
+    FoolsGoldFedAVGAlgorithm,
     GeometricMedianFedAVGAlgorithm,
     GraphAlgorithm,
     GraphNodeEmbeddingPassingAlgorithm,
@@ -74,6 +75,7 @@ __all__ = [
     "FedAVGAlgorithm",
     "FLTrustFedAVGAlgorithm",
     "FedAvgContext",
+    "FoolsGoldFedAVGAlgorithm",
     "GeometricMedianFedAVGAlgorithm",
     "GraphAlgorithm",
     "GraphNodeEmbeddingPassingAlgorithm",
@@ -189,6 +191,16 @@ def _register_builtin() -> None:
             client_cls=None,  # type: ignore[arg-type]
             server_cls=AggregationServer,
             algorithm_cls=FLTrustFedAVGAlgorithm,
+        )
+    # FoolsGold: the look-alikes among the clients' accumulated updates are down-weighted (a sybil defence)
+    if not AlgorithmRepository.has_algorithm("fed_foolsgold"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_foolsgold",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            algorithm_cls=FoolsGoldFedAVGAlgorithm,
         )
     # the FedOpt server optimisers (Reddi et al.): the learning rate of the adaptive ones has no
     # default, so the caller binds it (functools.partial(entry, learning_rate=...)); "fed_avgm" runs

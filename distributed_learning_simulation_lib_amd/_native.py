@@ -39,6 +39,7 @@ FLAG_INPUT_NAN = 0x8  # robust rules: a client tensor holds NaN
 ROBUST_TRIMMED_MEAN, ROBUST_MEDIAN = 0, 1  # FEDAVG_ROBUST_*: fedavg_robust_aggregate modes
 ROBUST_MAX_CLIENTS = 64
 KRUM_MAX_CLIENTS = 256  # FEDAVG_KRUM_MAX_CLIENTS: fedavg_pairwise_sqdist
+GRAM_MAX_CLIENTS = 256  # FEDAVG_GRAM_MAX_CLIENTS: fedavg_gram_about_point
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
 # fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta, fedavg_sign_aggregate_delta,
 # fedavg_sign_majority_vote
@@ -150,6 +151,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_fold_about_point": (
         c_int32, [c_void_p, _PP, c_int32, _PD, c_int32, c_double, _PP, _PP, c_int32, c_void_p]),
     "fedavg_moments_about_point": (c_int32, [c_void_p, _PP, c_int32, c_int32, _PP, _PP, c_void_p, c_void_p]),
+    "fedavg_gram_about_point": (c_int32, [c_void_p, _PP, c_int32, c_int32, _PP, _PP, _PP, c_void_p, c_void_p]),
     "fedavg_server_opt_step": (
         c_int32, [c_void_p, _PP, c_int32, _PD, c_int32, c_double, _PP, _PP, _PP, _PP, _PP, c_int32, c_double,
                   c_double, c_double, c_double, c_double, c_double, _PP, c_int32, c_void_p]),

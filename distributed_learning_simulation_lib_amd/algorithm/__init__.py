@@ -4,6 +4,7 @@ from .clipped_aggregation_algorithm import ClippedFedAVGAlgorithm
 from .composite_aggregation_algorithm import CompositeAggregationAlgorithm
 from .fed_avg_algorithm import FedAVGAlgorithm
 from .fltrust_aggregation_algorithm import FLTrustFedAVGAlgorithm
+from .foolsgold_aggregation_algorithm import FoolsGoldFedAVGAlgorithm
 from .geometric_median_algorithm import GeometricMedianFedAVGAlgorithm
 from .graph_algorithm import GraphAlgorithm
 from .graph_embedding_algorithm import GraphNodeEmbeddingPassingAlgorithm
@@ -17,7 +18,7 @@ from .sign_vote_algorithm import SignMajorityVoteAlgorithm
 from .sparse_fed_avg_algorithm import SparseFedAVGAlgorithm
 
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "CompositeAggregationAlgorithm",
-           "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
+           "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "FoolsGoldFedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
            "PersonalizedFedAVGAlgorithm",
            "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",

@@ -3009,6 +3009,7 @@ const SideModule kSideModules[FEDAVG_MODULES] = {
     {fedavg_internal_dp_constant, fedavg_internal_dp_release},
     {fedavg_internal_topk_constant, fedavg_internal_topk_release},
     {fedavg_internal_sign_constant, fedavg_internal_sign_release},
+    {fedavg_internal_gram_constant, fedavg_internal_gram_release},
 };
 
 bool side_constant(const char* name, int64_t* v) {

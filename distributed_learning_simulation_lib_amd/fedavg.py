@@ -34,7 +34,8 @@ import torch
 from . import _native
 from .rules import (  # noqa: F401 - re-exported: ``from ...fedavg import krum_select`` keeps working
     ROBUST_MODES, SERVER_OPT_MODES, _sqrt_rn, bulyan_select, check_robust_rule, check_server_opt,
-    clipping_coefficients, geometric_median_step, krum_select, robust_trim, server_opt_update, trust_coefficients,
+    clipping_coefficients, foolsgold_coefficients, geometric_median_step, krum_select, robust_trim, server_opt_update,
+    trust_coefficients,
 )
 from .sign import SignDelta, bit_bytes
 from .sparse import SparseDelta
@@ -938,6 +939,60 @@ class FedAvgContext:
             )
         )
         return out[0], out[1]
+
+    def gram_about_point(self, table: ClientTable, in_dtype: torch.dtype,
+                         point: Sequence[torch.Tensor] | None = None,
+                         history_in: Sequence[Sequence[torch.Tensor]] | None = None,
+                         history_out: Sequence[Sequence[torch.Tensor]] | None = None) -> torch.Tensor:
+        """The n x n fp64 Gram matrix (on the device) of the table's clients' whole updates about
+        ``point``, ``G[i][j] = sum_e r_i[e] * r_j[e]`` (``fedavg_gram_about_point``; not a reference
+        algorithm): the device half of FoolsGold. ``r_i = x_i - point`` (``None``: the
+        origin), or with the history tables ``r_i = history_in[i] + (x_i - point)``, which is also
+        stored to ``history_out[i]``: one rounded fp64 subtract and one rounded fp64 add per element.
+        The sum runs through the fp64 matrix instruction: exactly symmetric, the same bits on every
+        run, within ``(P + 2) * 2^-53 * sum_e |r_i r_j|`` of the exact value, but not restated bit
+        for bit on the CPU. ``point`` is one contiguous fp64 tensor per segment on the context's
+        device; ``history_in[i]`` and ``history_out[i]`` are such lists per client, with no storage
+        shared between an output and any input or other output. The table's weights are ignored
+        and the accumulator is not touched. Refused before any launch: an empty table, more than
+        256 clients, an absent entry, quantised records, a point or a history that does not match,
+        one history table without the other, shared history storage."""
+        self._refuse_before_table(table, in_dtype, "the Gram matrix", "s", _native.GRAM_MAX_CLIENTS)
+        p = self._whole_updates(table, in_dtype, "the Gram matrix compares")
+        zp = None if point is None else self._segment_array("point", point)
+        n, T = table.num_clients, self.layout.num_segments
+        if (history_in is None) != (history_out is None):
+            raise ValueError("history_in and history_out come together or not at all")
+        hi = ho = None
+        tabs: list[np.ndarray] = []  # the history pointer tables, alive until the call returns
+        if history_in is not None:
+            if len(history_in) != n or len(history_out) != n:
+                raise ValueError(f"one history_in and one history_out list per client is required: {n} clients")
+            for what, rows in (("history_in", history_in), ("history_out", history_out)):
+                for i, row in enumerate(rows):
+                    self._segment_array(f"{what}[{i}]", row)
+                tabs.append(np.array([z.data_ptr() for row in rows for z in row], dtype=np.uint64))
+            sizes = np.tile(np.asarray(self.layout.numels, dtype=np.uint64) * 8, n)
+            lo = np.concatenate(tabs)
+            hi_end = lo + np.concatenate([sizes, sizes])
+            is_out = np.arange(2 * n * T) >= n * T
+            order = np.argsort(lo, kind="stable")
+            lo, hi_end, is_out = lo[order], hi_end[order], is_out[order]
+            zero = np.zeros(1, dtype=np.uint64)
+            any_end = np.concatenate([zero, np.maximum.accumulate(hi_end)[:-1]])
+            out_end = np.concatenate([zero, np.maximum.accumulate(np.where(is_out, hi_end, 0))[:-1]])
+            if bool((lo < np.where(is_out, any_end, out_end)).any()):
+                raise ValueError("a history_out tensor shares storage with a history_in tensor or with another "
+                                 "history_out tensor")
+            hi, ho = (tab.ctypes.data_as(_PTR) for tab in tabs)
+        out = torch.empty((n, n), dtype=torch.float64, device=self.device)
+        _native.check(
+            self._lib.fedavg_gram_about_point(
+                self._h, p.ctypes.data_as(_PTR), dtype_code(in_dtype), n, zp, hi, ho,
+                ctypes.c_void_p(out.data_ptr()), self.stream,
+            )
+        )
+        return out
 
     def fold_about_point(self, table: ClientTable, in_dtype: torch.dtype, coefficients: Sequence[float],
                          divisor: float, point: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],

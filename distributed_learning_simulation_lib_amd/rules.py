@@ -1,5 +1,5 @@
 """Host arithmetic of the side rules: what the robust, Krum, Bulyan, geometric-median, clipping,
-FLTrust and server-optimiser algorithms compute on the CPU between two kernel calls, and on their CPU
+FLTrust, FoolsGold and server-optimiser algorithms compute on the CPU between two kernel calls, and on their CPU
 paths in place of them.
 
 Pure host code in plain Python floats (``server_opt_update`` alone works on torch CPU tensors): no
@@ -199,6 +199,55 @@ def trust_coefficients(dots: Sequence[float], sqnorms: Sequence[float],
         scores.append(score)
         coef.append(score * (n0 / ni))
     return scores, coef
+
+
+def foolsgold_coefficients(G: Any, kappa: float = 1.0) -> tuple[list[float], list[float]]:
+    """FoolsGold's client weights from the n x n Gram matrix of the clients' (accumulated) updates
+    (host arithmetic in plain Python floats, shared by the GPU and the CPU path; the
+    steps are those of the authors' published code). ``s_i = sqrt(G_ii)``;
+    ``cs_ij = G_ij / (s_i * s_j)`` for ``i != j`` (0.0 where the denominator is 0), ``cs_ii = 0.0``;
+    ``m_i = max_j cs_ij`` (the diagonal counts, so ``m_i >= 0``); pardoning: for ``i != j`` with
+    ``m_i < m_j``, ``cs_ij = cs_ij * m_i / m_j``; ``w_i = 1 - max_j cs_ij`` clipped to [0, 1];
+    ``W = max_i w_i``: 0 gives every alpha 0.0, otherwise ``w_i = w_i / W``, a ``w_i`` of exactly 1
+    becomes 0.99, and ``alpha_i = kappa * (ln(w_i / (1 - w_i)) + 0.5)`` clipped to [0, 1] (``ln 0``
+    is ``-inf`` and clips to 0). One client gets ``[1.0]``. Returns ``(alphas, max_cosines)`` with
+    ``max_cosines = m``. Refused: a matrix that is not square, a non-finite entry, a ``kappa`` that is
+    not finite and > 0."""
+    rows = [[float(x) for x in r] for r in (G.tolist() if hasattr(G, "tolist") else G)]
+    n = len(rows)
+    if n == 0 or any(len(r) != n for r in rows):
+        raise ValueError("the Gram matrix must be square and not empty")
+    kappa = float(kappa)
+    if not (kappa > 0 and math.isfinite(kappa)):
+        raise ValueError(f"kappa must be a finite number > 0, not {kappa}")
+    if not all(math.isfinite(x) for r in rows for x in r):
+        raise ValueError("the Gram matrix holds a non-finite entry")
+    if n == 1:
+        return [1.0], [0.0]
+    s = [math.sqrt(rows[i][i]) for i in range(n)]
+    cs = [[0.0] * n for _ in range(n)]
+    for i in range(n):
+        for j in range(n):
+            den = s[i] * s[j]
+            if i != j and den != 0:
+                cs[i][j] = rows[i][j] / den
+    m = [max(r) for r in cs]
+    for i in range(n):
+        for j in range(n):
+            if i != j and m[i] < m[j]:
+                cs[i][j] = cs[i][j] * m[i] / m[j]
+    w = [min(1.0, max(0.0, 1.0 - max(r))) for r in cs]
+    W = max(w)
+    if W == 0:
+        return [0.0] * n, m
+    alphas = []
+    for x in w:
+        x = x / W
+        if x == 1:
+            x = 0.99
+        a = kappa * (math.log(x / (1.0 - x)) + 0.5) if x > 0 else -math.inf
+        alphas.append(min(1.0, max(0.0, a)))
+    return alphas, m
 
 
 SERVER_OPT_MODES = ("avgm", "adagrad", "yogi", "adam")  # FEDAVG_OPT_AVGM / ADAGRAD / YOGI / ADAM in this order

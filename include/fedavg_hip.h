@@ -161,7 +161,10 @@ int32_t fedavg_build_flags(void);
  * "vote_group" (clients one carry-save tree takes before its carry ripples), "vote_loads" (clients
  * whose words a lane has in flight), "vote_small_clients" and "vote_mid_clients" (the largest client
  * counts of the kernel's 3-plane and 7-plane cases; above them it keeps 11 planes) of
- * fedavg_sign_majority_vote: none of them enters the result.
+ * fedavg_sign_majority_vote: none of them enters the result;
+ * "gram_chunk" (elements per workgroup), "gram_tile" (elements staged per step), "gram_block"
+ * (clients per row / column block), "gram_threads", "gram_max_clients" and "gram_ae_<d>" (elements of
+ * one 16-byte load) of fedavg_gram_about_point.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -562,6 +565,53 @@ int32_t fedavg_moments_about_point(fedavg_ctx* ctx, const void* const* client_pt
                                    const double* const* centre_ptrs /* [num_segments] fp64, or NULL: the origin */,
                                    const double* const* direction_ptrs /* [num_segments] fp64, required */,
                                    double* out /* [2][n], device: dots, then squared norms */, void* stream);
+
+/*
+ * The Gram matrix of the clients' whole updates about one fp64 point, optionally of their updates
+ * accumulated over the rounds: the device half of FoolsGold (Fung, Yoon, Beschastnikh, "The
+ * Limitations of Federated Learning in Sybil Settings", RAID 2020). NOT an algorithm of the
+ * reference: the contract is DESIGN.md §5y, restated independently in tests/foolsgold_reference.py.
+ *
+ * client_ptrs[num_clients][num_segments], every entry non-NULL; in_dtype FEDAVG_F32 / F16 / BF16 /
+ * F64 (no records, no deltas). point_ptrs[num_segments] is a host array of device pointers to fp64
+ * tensors of the segments' element counts, 8-byte aligned; NULL is the origin. history_in and
+ * history_out are [num_clients][num_segments] host arrays of device pointers to fp64 tensors of the
+ * segments' element counts, 8-byte aligned; both or neither. For client i and every element e of
+ * every segment, with every client value converted exactly to fp64:
+ *   d = x_i[e] - v[e]                      one rounded fp64 subtract (no point: d = x_i[e])
+ *   h = history_in_i[e] + d                one rounded fp64 add, no FMA; history_out_i[e] = h
+ *   r_i[e] = h with history, d without
+ *   out[i * n + j] = sum_e r_i[e] * r_j[e]
+ * `out` is device memory, n * n doubles. The sum is accumulated by the fp64 matrix instruction
+ * (v_mfma_f64_16x16x4_f64): the products are fused into the sum and the order of the four products
+ * of one instruction is the hardware's, so the matrix is NOT restated bit for bit on the CPU. Every
+ * entry is within (P + 2) * 2^-53 * sum_e |r_i[e] * r_j[e]| of the exact sum whatever the order (P =
+ * the layout's element count). It is deterministic: the layout is cut, segment by segment, into
+ * chunks of "gram_chunk" elements; a workgroup owns one chunk for one pair of "gram_block"-client
+ * blocks and issues its matrix instructions in ascending order; the chunk partials go to a
+ * workspace and a second kernel, ordered after the first by the stream, adds them in ascending chunk
+ * order. No floating-point atomics; the same call twice gives the same bits, whatever the CU count
+ * or timing. Only entries with i <= j are computed, then mirrored: `out` is exactly symmetric.
+ * history_out is bit for bit the two operations above. It is written by exactly one workgroup per
+ * (row block, chunk) while other workgroups read history_in, so no history_out tensor may share a
+ * byte with a history_in tensor or with another history_out tensor.
+ * Asynchronous on `stream`; the accumulator is not touched; nothing outside a tensor is read or
+ * written. Slots past a chunk's end or past the last client hold +0.0 and reach no entry of `out`.
+ * A NaN in a client, the point or the history latches FEDAVG_FLAG_INPUT_NAN (tested at the load); a
+ * NaN in an entry of `out` (0 * inf, +inf + -inf) latches FEDAVG_FLAG_ACC_NAN (tested on the result).
+ * Refused before any launch, with the flags, `out` and history_out untouched: FEDAVG_ERR_INVALID (a
+ * NULL client table or out; a NULL client, point or history entry; one history table without the
+ * other; history tensors that share storage as above; a bad dtype; a client pointer not aligned to
+ * its element size; a point, history or out pointer not aligned to 8 bytes; num_clients < 1 or
+ * > FEDAVG_GRAM_MAX_CLIENTS), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_GRAM_MAX_CLIENTS 256
+int32_t fedavg_gram_about_point(fedavg_ctx* ctx, const void* const* client_ptrs, int32_t in_dtype,
+                                int32_t num_clients,
+                                const double* const* point_ptrs /* [num_segments] fp64, or NULL: the origin */,
+                                const double* const* history_in /* [n][num_segments] fp64, or NULL */,
+                                double* const* history_out /* [n][num_segments] fp64; NULL iff history_in is NULL */,
+                                double* out /* [n][n], device */, void* stream);
 
 /*
  * The server optimiser step: the fold about a point with the FedOpt epilogue fused onto it (Reddi et
