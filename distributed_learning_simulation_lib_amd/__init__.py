@@ -23,6 +23,7 @@ from .algorithm import (
     KrumFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
+    SecAggFedAVGAlgorithm,
     ServerOptFedAVGAlgorithm,
     SignFedAVGAlgorithm,
     SignMajorityVoteAlgorithm,
@@ -56,6 +57,7 @@ from .quantized import (
     StochasticQuantClientEndpoint,
     philox_uniforms,
 )
+from .secagg import MaskedDelta, SecAggEndpoint, SecAggSession, secagg_mask_parameter
 from .sign import SignDelta, SignEndpoint, SignErrorFeedback, sign_compress, sign_compress_parameter
 from .sparse import SparseDelta, TopKErrorFeedback, TopKSparseEndpoint, topk_sparsify, topk_sparsify_parameter
 
@@ -92,6 +94,9 @@ __all__ = [
     "PersonalizedFedAVGAlgorithm",
     "QuantClientEndpoint",
     "RobustFedAVGAlgorithm",
+    "SecAggEndpoint",
+    "SecAggFedAVGAlgorithm",
+    "SecAggSession",
     "ServerOptFedAVGAlgorithm",
     "SignDelta",
     "SignEndpoint",
@@ -109,6 +114,7 @@ __all__ = [
     "get_message_size",
     "normal_stream",
     "philox_uniforms",
+    "secagg_mask_parameter",
     "sign_compress",
     "sign_compress_parameter",
     "topk_sparsify",
@@ -287,6 +293,19 @@ def _register_builtin() -> None:
                 algorithm_cls=SignMajorityVoteAlgorithm,
                 **endpoint,
             )
+    # FedAvg under secure aggregation: the unmasking rule behind the masking endpoint. The session seed has no
+    # default: the caller binds it on both sides (functools.partial(entry, session_seed=...) and the endpoint's
+    # keyword arguments session_seed, frac_bits, value_bits)
+    if not AlgorithmRepository.has_algorithm("fed_avg_secagg"):
+        from .server import AggregationServer
+
+        AlgorithmRepository.register_algorithm(
+            algorithm_name="fed_avg_secagg",
+            client_cls=None,  # type: ignore[arg-type]
+            server_cls=AggregationServer,
+            client_endpoint_cls=SecAggEndpoint,
+            algorithm_cls=SecAggFedAVGAlgorithm,
+        )
     # FedAvg whose workers send their updates, and receive the broadcast, as QSGD or NNADQ records: the
     # plain server and rule (which folds records as they are) behind the quantised client endpoints. The
     # NNADQ weight has no default: the caller binds it through the endpoint's keyword arguments

@@ -43,6 +43,7 @@ GRAM_MAX_CLIENTS = 256  # FEDAVG_GRAM_MAX_CLIENTS: fedavg_gram_about_point
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
 # fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta, fedavg_sign_aggregate_delta,
 # fedavg_sign_majority_vote
+SECAGG_MAX_CLIENTS = 1024  # FEDAVG_SECAGG_MAX_CLIENTS: fedavg_secagg_unmask
 ROUTE_MAX_SOURCES = 1024  # fedavg_route_rows
 ROUTE_MAX_NODE_SPACE = 1 << 28
 ROUTE_ERR_DUPLICATE, ROUTE_ERR_ORDER, ROUTE_ERR_RANGE = 1, 2, 4  # bits of fedavg_route_errors
@@ -180,6 +181,13 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     # signSGD's majority vote over the same bits (sign_kernels.hip); the bit and mask tables as raw addresses
     "fedavg_sign_majority_vote": (
         c_int32, [c_void_p, c_void_p, c_int32, _PD, _PP, _PP, c_int32, c_void_p, c_void_p, c_void_p]),
+    # secure aggregation by pairwise masking (secagg_kernels.hip); tables as raw addresses
+    "fedavg_secagg_mask": (
+        c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_uint32, c_void_p,
+                  c_void_p, c_int32, c_void_p, c_void_p]),
+    "fedavg_secagg_unmask": (
+        c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_uint32, c_int32, c_double, _PP, _PP,
+                  c_int32, c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

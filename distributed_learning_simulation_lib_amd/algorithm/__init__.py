@@ -12,6 +12,7 @@ from .graph_topology_algorithm import GraphTopologyAlgorithm
 from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
+from .secagg_fed_avg_algorithm import SecAggFedAVGAlgorithm
 from .server_opt_algorithm import ServerOptFedAVGAlgorithm
 from .sign_fed_avg_algorithm import SignFedAVGAlgorithm
 from .sign_vote_algorithm import SignMajorityVoteAlgorithm
@@ -21,5 +22,5 @@ __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgori
            "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "FoolsGoldFedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
            "PersonalizedFedAVGAlgorithm",
-           "RobustFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
+           "RobustFedAVGAlgorithm", "SecAggFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
            "SparseFedAVGAlgorithm"]

@@ -3010,6 +3010,7 @@ const SideModule kSideModules[FEDAVG_MODULES] = {
     {fedavg_internal_topk_constant, fedavg_internal_topk_release},
     {fedavg_internal_sign_constant, fedavg_internal_sign_release},
     {fedavg_internal_gram_constant, fedavg_internal_gram_release},
+    {fedavg_internal_secagg_constant, fedavg_internal_secagg_release},
 };
 
 bool side_constant(const char* name, int64_t* v) {

@@ -503,6 +503,35 @@ def _stream_ids(seed: int, draw: int, tensor_ids: Sequence[int] | None, T: int) 
     return ids
 
 
+def _secagg_scalars(weight: int, frac_bits: int, value_bits: int) -> tuple[int, int, int]:
+    """The integer arguments of the secure-aggregation calls, in range."""
+    if isinstance(weight, float) and not weight.is_integer():
+        raise ValueError(f"the weight is an integer: {weight} is not one (scale the weights to integers first)")
+    weight, frac_bits, value_bits = int(weight), int(frac_bits), int(value_bits)
+    if not 0 <= weight < 1 << 31:
+        raise ValueError(f"the weight is an integer in 0 .. 2^31 - 1, not {weight}")
+    if not 0 <= frac_bits <= 52:
+        raise ValueError(f"frac_bits is in 0 .. 52, not {frac_bits}")
+    if not 1 <= value_bits <= 62:
+        raise ValueError(f"value_bits is in 1 .. 62, not {value_bits}")
+    return weight, frac_bits, value_bits
+
+
+def _secagg_seeds(seeds: Sequence[int], signs: Sequence[int], draw: int, least: int) -> tuple[np.ndarray, np.ndarray]:
+    """The seed table of a secure-aggregation call as its C-ABI arrays."""
+    if not 0 <= int(draw) < 1 << 32:
+        raise ValueError("the draw is a uint32")
+    if any(not 0 <= int(s) < 1 << 64 for s in seeds):
+        raise ValueError("a seed is a uint64")
+    sd = np.array([int(s) for s in seeds], dtype=np.uint64)
+    sg = np.array([int(s) for s in signs], dtype=np.int32)
+    if sd.shape != sg.shape or sd.size < least or sd.size > 1 << 20:
+        raise ValueError(f"one sign per seed and between {least} and 2^20 seeds are required")
+    if sg.size and not (np.abs(sg) == 1).all():
+        raise ValueError("a sign is +1 or -1")
+    return sd, sg
+
+
 class FedAvgContext:
     """One native FedAvg context: layout + device + fp64 accumulator."""
 
@@ -1323,6 +1352,93 @@ class FedAvgContext:
             self._lib.fedavg_sign_majority_vote(
                 self._h, table.bptr.ctypes.data, table.num_clients, s.ctypes.data_as(_DBL), zp, op, ocode,
                 *(None if m is None else m.ctypes.data for m in masks), self.stream,
+            )
+        )
+
+    def secagg_mask(self, tensors: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weight: int,
+                    seeds: Sequence[int], signs: Sequence[int], draw: int, frac_bits: int = 24,
+                    value_bits: int = 40) -> None:
+        """A secure-aggregation client's masked update in one launch (``fedavg_secagg_mask``, DESIGN.md
+        §5z; not a reference algorithm): ``outs[t][e] = rint(tensors[t][e] * 2^frac_bits) * weight +
+        sum_s signs[s] * m(seeds[s], draw, t, e)`` in the ring Z/2^64. ``tensors`` are non-empty
+        contiguous tensors of one floating dtype on the context's device, of any sizes (the context's
+        layout plays no part); ``outs[t]`` is a contiguous int64 tensor of the size of ``tensors[t]``.
+        ``weight`` is an integer in 0 .. 2^31 - 1, ``seeds`` uint64 values with ``signs`` +1 or -1.
+        Asynchronous; an element that is not finite or whose ``|rint(x * 2^frac_bits)|`` reaches
+        ``2^value_bits`` latches the input flag (``flags()``)."""
+        T = len(tensors)
+        if T == 0 or len(outs) != T:
+            raise ValueError("one output per tensor and at least one tensor are required")
+        weight, frac_bits, value_bits = _secagg_scalars(weight, frac_bits, value_bits)
+        sd, sg = _secagg_seeds(seeds, signs, draw, 1)
+        dt = tensors[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the masking step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        ns = [x.numel() for x in tensors]
+        t, fault = _first(T, self._first_unfit(tensors, dt), next((t for t, n in enumerate(ns) if n == 0), T),
+                          self._first_unfit(outs, torch.int64, ns))
+        if fault == 0:
+            raise self._flat_refusal("tensor", t, dt)
+        if fault == 1:
+            raise ValueError(f"tensor {t}: an empty tensor has no masked words, and is the caller's")
+        if fault == 2:
+            raise self._flat_refusal("output", t, torch.int64, ns[t])
+        iptr, optr, ns = _addresses(tensors, ns), _addresses(outs, ns), np.array(ns, dtype=np.int64)
+        _native.check(
+            self._lib.fedavg_secagg_mask(
+                self._h, DTYPE_CODES[dt], iptr.ctypes.data, ns.ctypes.data, T, weight, frac_bits, value_bits,
+                int(draw), sd.ctypes.data, sg.ctypes.data, len(sd), optr.ctypes.data, self.stream,
+            )
+        )
+
+    def secagg_unmask(self, rows: Sequence[Sequence[torch.Tensor]], seeds: Sequence[int], signs: Sequence[int],
+                      draw: int, frac_bits: int, total_weight: float, base: Sequence[torch.Tensor] | None,
+                      outs: Sequence[torch.Tensor], out_dtype: torch.dtype = torch.float64) -> None:
+        """The server's half in one launch (``fedavg_secagg_unmask``): per element of
+        segment ``t``, ``S = sum_i rows[i][t][e] + sum_s signs[s] * m(seeds[s], draw, t, e)`` in Z/2^64,
+        then ``outs[t][e] = base[t][e] + ((double)(int64)S * 2^-frac_bits) / total_weight`` (without a
+        base: the quotient). ``rows[i][t]`` is reporting client ``i``'s contiguous int64 tensor of
+        segment ``t`` on the context's device; ``base`` one contiguous fp64 tensor per segment or
+        ``None``; ``outs`` one contiguous ``out_dtype`` tensor per segment, none of them its base or a
+        client. The accumulator is not touched; the NaN flags (a NaN base: input; ``total_weight``
+        0: result) are the caller's to read. Refused before any launch: no clients, more than 1024, a
+        tensor that does not match its segment, ``frac_bits`` outside 0 .. 52, a total weight that is
+        negative or not finite."""
+        ocode = out_code(out_dtype)
+        n, T, numels = len(rows), self.layout.num_segments, self.layout.numels
+        if n == 0:
+            raise ValueError("the unmasking step of no clients")
+        if n > _native.SECAGG_MAX_CLIENTS:
+            raise NotImplementedError(f"{n} clients: the unmasking step takes at most {_native.SECAGG_MAX_CLIENTS}")
+        _, frac_bits, _ = _secagg_scalars(0, frac_bits, 1)
+        sd, sg = _secagg_seeds(seeds, signs, draw, 0)
+        total_weight = float(total_weight)
+        if not (total_weight >= 0 and math.isfinite(total_weight)):
+            raise ValueError(f"the total weight must be finite and >= 0, not {total_weight}")
+        if len(outs) != T or (base is not None and len(base) != T):
+            raise ValueError("one output tensor (and one base tensor) per segment is required")
+        for i, row in enumerate(rows):
+            t = self._first_unfit(row, torch.int64, numels) if len(row) == T else 0
+            if t < T:
+                raise ValueError(f"client {i}, tensor {t}: a contiguous int64 tensor of {numels[t]} elements on "
+                                 f"{self.device} is required, one per segment")
+        t, fault = _first(T, self._first_unfit(base, torch.float64, numels) if base is not None else T,
+                          self._first_unfit(outs, out_dtype, numels),
+                          _first_shared(base, outs) if base is not None else T,
+                          min(_first_shared(row, outs) for row in rows))
+        if fault == 0:
+            raise self._segment_refusal("base", t)
+        if fault == 1:
+            raise self._segment_refusal("output", t, out_dtype)
+        if fault >= 2:
+            raise ValueError(f"output tensor {t} is its {'base' if fault == 2 else 'client'}: the unmasking step "
+                             "is not in-place")
+        cptr = np.array([z.data_ptr() for row in rows for z in row], dtype=np.uint64)
+        _native.check(
+            self._lib.fedavg_secagg_unmask(
+                self._h, cptr.ctypes.data, n, sd.ctypes.data, sg.ctypes.data, len(sd), int(draw), frac_bits,
+                total_weight, None if base is None else _pointer_array(base), _pointer_array(outs), ocode,
+                self.stream,
             )
         )
 

@@ -35,6 +35,7 @@ from ..message import (
     wire_class,
 )
 from ..quantized import dequantize_parameter, is_quantized
+from ..secagg import is_masked
 from ..sign import densify_parameter as densify_sign_parameter
 from ..sign import is_sign
 from ..sparse import densify_parameter, is_sparse
@@ -201,6 +202,12 @@ class AggregationServer:
         if is_delta_message(data) and is_sign(data.delta_parameter):
             if not getattr(self._algorithm, "accepts_sign_messages", False):
                 data.delta_parameter = densify_sign_parameter(data.delta_parameter)
+        # ``secagg.MaskedDelta`` values cannot be densified: one client's words are noise, and only
+        # an algorithm with ``accepts_masked_messages`` (SecAggFedAVGAlgorithm) can remove the masks
+        if is_delta_message(data) and is_masked(data.delta_parameter):
+            if not getattr(self._algorithm, "accepts_masked_messages", False):
+                raise TypeError(f"{type(self._algorithm).__name__} cannot take masked (secure aggregation) updates: "
+                                "they are decoded only as a round's sum, by SecAggFedAVGAlgorithm")
 
     def _aggregate_worker_data(self) -> Message:
         self._algorithm.set_old_parameter(self._model_cache.parameter)

@@ -164,7 +164,12 @@ int32_t fedavg_build_flags(void);
  * fedavg_sign_majority_vote: none of them enters the result;
  * "gram_chunk" (elements per workgroup), "gram_tile" (elements staged per step), "gram_block"
  * (clients per row / column block), "gram_threads", "gram_max_clients" and "gram_ae_<d>" (elements of
- * one 16-byte load) of fedavg_gram_about_point.
+ * one 16-byte load) of fedavg_gram_about_point;
+ * "secagg_tile" (elements of a wave's tile), "secagg_blocks" (Philox blocks, of two elements each, a
+ * lane owns), "secagg_loads" (clients whose vectors a lane has in flight), "secagg_split" (seed
+ * entries from which the four waves of a workgroup share one tile and the seed entries, and the
+ * clients, between them), "secagg_threads" and "secagg_max_seeds" of fedavg_secagg_mask and
+ * fedavg_secagg_unmask: none of them enters the result.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -1050,6 +1055,65 @@ int32_t fedavg_sign_majority_vote(fedavg_ctx* ctx, const void* const* bit_ptrs /
                                   void* const* out_ptrs /* [T], device */, int32_t out_dtype,
                                   void* const* neg_ptrs /* [T] device, or NULL */,
                                   void* const* tie_ptrs /* [T] device, or NULL */, void* stream);
+
+/*
+ * Secure aggregation by pairwise masking (Bonawitz et al., "Practical Secure Aggregation for
+ * Privacy-Preserving Machine Learning", CCS 2017): the two device halves. Not an algorithm of the
+ * reference; tests/secagg_reference.py restates the contract in numpy. All sums are in
+ * the ring Z/2^64, so no order is part of the contract: the result is the same bits however the work
+ * is split. Neither the key agreement nor the secret sharing of the protocol is here: the seeds are
+ * the caller's, and Philox is not a cryptographic generator.
+ *
+ * Encoding. For an element x widened exactly to fp64, a weight w (an integer, 0 <= w < 2^31),
+ * frac_bits f in 0 .. 52 and value_bits in 1 .. 62:
+ *   t = x * 2^f (exact);  r = rint(t) (to nearest, ties to even);
+ *   x is out of range if it is not finite or |r| >= 2^value_bits: it latches FEDAVG_FLAG_INPUT_NAN
+ *   (its output word is then unspecified but stays inside the buffer);
+ *   q = (uint64)(int64)r * w mod 2^64.
+ * The mask stream. m(seed, draw, t, e) is a 64-bit word of the Philox4x32-10 block with key
+ * (seed & 0xffffffff, seed >> 32) and counter (b & 0xffffffff, b >> 32, t, draw), b = e / 2: the block's
+ * words w0 | w1 << 32 for an even e, w2 | w3 << 32 for an odd e (the counter and key convention of
+ * fedavg_dp_noise). t is the tensor's position in the call, e the element, draw the round.
+ *
+ * fedavg_secagg_mask, the client's step over num_tensors device tensors of one dtype (FEDAVG_F32 / F16
+ * / BF16 / F64), tensor t of numels[t] (host, 1 .. 2^31 - 1) elements at in_ptrs[t], aligned to the
+ * element:
+ *   out_ptrs[t][e] = q[e] + sum over the num_seeds entries s of signs[s] * m(seeds[s], draw, t, e)  mod 2^64
+ * as int64 words, 8-byte aligned. seeds and signs (+1 or -1) are host arrays: the caller lists its self
+ * seed with +1 and the pair seed of every other worker j with +1 where its own id is below j, -1
+ * where it is above. One launch whatever num_tensors is.
+ *
+ * fedavg_secagg_unmask, the server's step over the context's layout: client_ptrs[i * T + t] holds the
+ * masked words of reporting client i for segment t (int64, 8-byte aligned), and per element
+ *   S = sum_i client_i[e] + sum_s signs[s] * m(seeds[s], draw, t, e)  mod 2^64
+ * (the caller lists every survivor's self seed with -1 and, for every survivor i and dropped worker d,
+ * their pair seed with -1 where i < d and +1 where i > d: S is then the sum of the survivors' q);
+ *   v = (double)(int64)S (one rounding to nearest even);  u = v * 2^-f;  g = u / total_weight (IEEE
+ *   division);  out = base_ptrs[t][e] + g (one rounded add) or, with base_ptrs NULL, out = g;
+ * an fp32 output is that value rounded once more. A NaN g (total_weight 0 with S 0) latches
+ * FEDAVG_FLAG_RESULT_NAN, a NaN in the base FEDAVG_FLAG_INPUT_NAN. One launch.
+ *
+ * Both: nothing outside a tensor is read or written; the accumulator and its state are not touched;
+ * no atomics; asynchronous on `stream`; the tables travel through the context, so calls on one context
+ * are ordered by their stream. Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype; a NULL
+ * table or entry other than base_ptrs; num_tensors < 1 or > 2^20; numels[t] < 1 or > 2^31 - 1;
+ * num_clients < 1 or > FEDAVG_SECAGG_MAX_CLIENTS; num_seeds < 1 (mask) or < 0 (unmask) or > 2^20; a sign
+ * other than +1 / -1; a weight outside 0 .. 2^31 - 1; frac_bits outside 0 .. 52; value_bits outside
+ * 1 .. 62; a total weight that is negative or not finite; a misaligned buffer; an output that is its
+ * input, its base or a client), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_SECAGG_MAX_CLIENTS 1024
+int32_t fedavg_secagg_mask(fedavg_ctx* ctx, int32_t dtype, const void* const* in_ptrs /* [T], device */,
+                           const int64_t* numels /* [T], host */, int32_t num_tensors, int64_t weight,
+                           int32_t frac_bits, int32_t value_bits, uint32_t draw,
+                           const uint64_t* seeds /* [num_seeds], host */, const int32_t* signs /* [num_seeds], host */,
+                           int32_t num_seeds, void* const* out_ptrs /* [T], device int64 */, void* stream);
+int32_t fedavg_secagg_unmask(fedavg_ctx* ctx, const void* const* client_ptrs /* [n][T], device int64 */,
+                             int32_t num_clients, const uint64_t* seeds /* [num_seeds], host */,
+                             const int32_t* signs /* [num_seeds], host */, int32_t num_seeds, uint32_t draw,
+                             int32_t frac_bits, double total_weight,
+                             const double* const* base_ptrs /* [T], device fp64, or NULL */,
+                             void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
