@@ -21,6 +21,7 @@ from .algorithm import (
     GraphNodeEmbeddingPassingAlgorithm,
     GraphTopologyAlgorithm,
     KrumFedAVGAlgorithm,
+    LowRankFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
     SecAggFedAVGAlgorithm,
@@ -39,6 +40,13 @@ from .dp import (
     normal_stream,
 )
 from .fedavg import ClientTable, FedAvgContext, ModelLayout, NaNAggregationError
+from .lowrank import (
+    LowRankDelta,
+    LowRankEndpoint,
+    LowRankErrorFeedback,
+    lowrank_compress,
+    lowrank_compress_parameter,
+)
 from .message import (
     DeltaParameterMessage,
     FeatureMessage,
@@ -83,6 +91,10 @@ __all__ = [
     "GraphNodeEmbeddingPassingAlgorithm",
     "GraphTopologyAlgorithm",
     "KrumFedAVGAlgorithm",
+    "LowRankDelta",
+    "LowRankEndpoint",
+    "LowRankErrorFeedback",
+    "LowRankFedAVGAlgorithm",
     "Message",
     "ModelLayout",
     "ModelParameter",
@@ -112,6 +124,8 @@ __all__ = [
     "add_dp_noise_to_parameter",
     "compute_dp_sigma",
     "get_message_size",
+    "lowrank_compress",
+    "lowrank_compress_parameter",
     "normal_stream",
     "philox_uniforms",
     "secagg_mask_parameter",
@@ -291,6 +305,20 @@ def _register_builtin() -> None:
                 client_cls=None,  # type: ignore[arg-type]
                 server_cls=AggregationServer,
                 algorithm_cls=SignMajorityVoteAlgorithm,
+                **endpoint,
+            )
+    # FedAvg over low-rank factor pairs, folded from the factors, and the same with workers that compress
+    # their diffs before sending (one power-iteration step with error feedback, rank 4 unless the caller
+    # binds another through the endpoint's keyword arguments)
+    for name, endpoint in (("fed_avg_lowrank", {}), ("fed_avg_lowrank_ef", {"client_endpoint_cls": LowRankEndpoint})):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=LowRankFedAVGAlgorithm,
                 **endpoint,
             )
     # FedAvg under secure aggregation: the unmasking rule behind the masking endpoint. The session seed has no

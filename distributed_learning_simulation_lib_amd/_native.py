@@ -42,7 +42,8 @@ KRUM_MAX_CLIENTS = 256  # FEDAVG_KRUM_MAX_CLIENTS: fedavg_pairwise_sqdist
 GRAM_MAX_CLIENTS = 256  # FEDAVG_GRAM_MAX_CLIENTS: fedavg_gram_about_point
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
 # fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta, fedavg_sign_aggregate_delta,
-# fedavg_sign_majority_vote
+# fedavg_sign_majority_vote, fedavg_lowrank_aggregate_delta
+LOWRANK_MAX_RANK = 16  # FEDAVG_LOWRANK_MAX_RANK: fedavg_lowrank_aggregate_delta
 SECAGG_MAX_CLIENTS = 1024  # FEDAVG_SECAGG_MAX_CLIENTS: fedavg_secagg_unmask
 ROUTE_MAX_SOURCES = 1024  # fedavg_route_rows
 ROUTE_MAX_NODE_SPACE = 1 << 28
@@ -188,6 +189,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_secagg_unmask": (
         c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_uint32, c_int32, c_double, _PP, _PP,
                   c_int32, c_void_p]),
+    # FedAvg over low-rank factor pairs (lowrank_kernels.hip); the factor tables as raw addresses
+    "fedavg_lowrank_aggregate_delta": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, _PD, c_int32, c_double, _PP, _PP, c_int32,
+                  c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

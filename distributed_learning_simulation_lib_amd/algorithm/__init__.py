@@ -10,6 +10,7 @@ from .graph_algorithm import GraphAlgorithm
 from .graph_embedding_algorithm import GraphNodeEmbeddingPassingAlgorithm
 from .graph_topology_algorithm import GraphTopologyAlgorithm
 from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
+from .lowrank_fed_avg_algorithm import LowRankFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 from .secagg_fed_avg_algorithm import SecAggFedAVGAlgorithm
@@ -21,6 +22,6 @@ from .sparse_fed_avg_algorithm import SparseFedAVGAlgorithm
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "CompositeAggregationAlgorithm",
            "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "FoolsGoldFedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
-           "PersonalizedFedAVGAlgorithm",
+           "LowRankFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
            "RobustFedAVGAlgorithm", "SecAggFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
            "SparseFedAVGAlgorithm"]

@@ -3011,6 +3011,7 @@ const SideModule kSideModules[FEDAVG_MODULES] = {
     {fedavg_internal_sign_constant, fedavg_internal_sign_release},
     {fedavg_internal_gram_constant, fedavg_internal_gram_release},
     {fedavg_internal_secagg_constant, fedavg_internal_secagg_release},
+    {fedavg_internal_lowrank_constant, fedavg_internal_lowrank_release},
 };
 
 bool side_constant(const char* name, int64_t* v) {

@@ -37,6 +37,7 @@ from .rules import (  # noqa: F401 - re-exported: ``from ...fedavg import krum_s
     clipping_coefficients, foolsgold_coefficients, geometric_median_step, krum_select, robust_trim, server_opt_update,
     trust_coefficients,
 )
+from .lowrank import LowRankDelta
 from .sign import SignDelta, bit_bytes
 from .sparse import SparseDelta
 
@@ -444,6 +445,51 @@ class SignBitTable:
                     raise ValueError(f"client {i}, tensor {t}: a contiguous sign delta of {numel} elements on "
                                      f"{device} is required")
                 self.bptr[i * T + t] = d.bits.data_ptr()
+        self.num_clients = n
+        self.layout = layout
+        self.device = device
+        self._keep = [list(row) for row in rows]
+
+
+class LowRankTable:
+    """Rows of low-rank deltas as the C-ABI arrays of ``fedavg_lowrank_aggregate_delta``: ``rows[i][t]``
+    is client ``i``'s ``LowRankDelta`` of segment ``t`` of ``layout`` on ``device``; the clients of a
+    segment share its row count and rank, and all factors one dtype (built once, reusable across
+    calls; it keeps the tensors alive)."""
+
+    def __init__(self, rows: Sequence[Sequence[LowRankDelta]], layout: ModelLayout, device: torch.device) -> None:
+        n, T = len(rows), layout.num_segments
+        dtypes = set()
+        self.lptr = np.zeros(n * T, dtype=np.uint64)
+        self.rptr = np.zeros(n * T, dtype=np.uint64)
+        self.m = np.zeros(T, dtype=np.int32)
+        self.rank = np.zeros(T, dtype=np.int32)
+        for i, row in enumerate(rows):
+            if len(row) != T:
+                raise ValueError(f"client {i}: one low-rank delta per segment is required")
+            for t, (d, numel) in enumerate(zip(row, layout.numels)):
+                if not isinstance(d, LowRankDelta):
+                    raise TypeError(f"client {i}, tensor {t}: a LowRankDelta is required, not {type(d).__name__}")
+                m, r = int(d.shape[0]), d.rank
+                if m < 1 or d.numel != numel or d.left.device != device or d.right.device != device \
+                        or tuple(d.left.shape) != (m, r) or tuple(d.right.shape) != (r, numel // m) \
+                        or not d.left.is_contiguous() or not d.right.is_contiguous():
+                    raise ValueError(f"client {i}, tensor {t}: contiguous [m, r] and [r, n] factors of {numel} = m n "
+                                     f"elements on {device} are required")
+                if r > _native.LOWRANK_MAX_RANK:
+                    raise NotImplementedError(f"client {i}, tensor {t}: rank {r}: the low-rank fold takes at most "
+                                              f"{_native.LOWRANK_MAX_RANK}")
+                if i == 0:
+                    self.m[t], self.rank[t] = m, r
+                elif (m, r) != (int(self.m[t]), int(self.rank[t])):
+                    raise ValueError(f"client {i}, tensor {t}: [{m}, {r}] left factor where client 0 sent "
+                                     f"[{self.m[t]}, {self.rank[t]}]: the clients of a tensor share one rank")
+                dtypes.add(d.dtype)
+                self.lptr[i * T + t] = d.left.data_ptr()
+                self.rptr[i * T + t] = d.right.data_ptr()
+        if len(dtypes) > 1:
+            raise ValueError(f"the factors of one call share one dtype, not {sorted(map(str, dtypes))}")
+        self.dtype = dtypes.pop() if dtypes else torch.float32
         self.num_clients = n
         self.layout = layout
         self.device = device
@@ -1306,6 +1352,39 @@ class FedAvgContext:
             self._lib.fedavg_sign_aggregate_delta(
                 self._h, table.bptr.ctypes.data, table.sptr.ctypes.data, dtype_code(table.dtype),
                 w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
+            )
+        )
+
+    def lowrank_aggregate_delta(self, rows: Sequence[Sequence[LowRankDelta]] | LowRankTable, weights: Sequence[float],
+                                divisor: float, base: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                                out_dtype: torch.dtype = torch.float64) -> None:
+        """FedAvg of low-rank deltas against ``base`` in one launch (``fedavg_lowrank_aggregate_delta``,
+        DESIGN.md §5aa): per tensor ``outs[t] = base[t] + (sum_i w_i L_i R_i) / divisor``, the sum one
+        ``[m, N r] [N r, n]`` product on the fp64 matrix unit: ``a_i = w_i * L_i`` rounded once, the
+        products fused into the sum in ascending ``(i, j)`` four to an instruction. The rule's own
+        contract: not the bits of ``aggregate_delta`` on the densified deltas unless every operation
+        is exact. ``rows[i][t]`` is client ``i``'s ``LowRankDelta`` of segment ``t`` on the context's
+        device (or a ``LowRankTable`` built from such rows once). ``base`` is one contiguous fp64
+        tensor per segment, ``outs`` one contiguous ``out_dtype`` tensor per segment, none of them its
+        base's own storage. The accumulator is not touched; the NaN flags are the caller's to read
+        (``raise_on_nan``). Refused before any launch: no clients, more than 1024, factors that do not
+        match their segment, ranks that differ inside a tensor or exceed the maximum, mixed factor
+        dtypes, a non-finite weight, a divisor that is not finite and > 0, a base or an output that
+        does not match, an output that is its base."""
+        ocode = out_code(out_dtype)
+        table = rows if isinstance(rows, LowRankTable) else LowRankTable(rows, self.layout, self.device)
+        if table.layout != self.layout or table.device != self.device:
+            raise ValueError("the low-rank table was built for another layout or device")
+        self._refuse_before_table(table, table.dtype, "the low-rank fold", "s", _native.POINT_MAX_CLIENTS)
+        n = table.num_clients
+        w = _client_scalars(weights, n, "weight")
+        divisor = _divisor(divisor)
+        zp, op = self._source_and_outputs("base", base, outs, out_dtype, "the low-rank fold is not in-place")
+        _native.check(
+            self._lib.fedavg_lowrank_aggregate_delta(
+                self._h, table.lptr.ctypes.data, table.rptr.ctypes.data, dtype_code(table.dtype),
+                table.m.ctypes.data, table.rank.ctypes.data, w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode,
+                self.stream,
             )
         )
 

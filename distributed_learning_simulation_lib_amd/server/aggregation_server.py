@@ -36,6 +36,8 @@ from ..message import (
 )
 from ..quantized import dequantize_parameter, is_quantized
 from ..secagg import is_masked
+from ..lowrank import densify_parameter as densify_lowrank_parameter
+from ..lowrank import is_lowrank
 from ..sign import densify_parameter as densify_sign_parameter
 from ..sign import is_sign
 from ..sparse import densify_parameter, is_sparse
@@ -202,6 +204,11 @@ class AggregationServer:
         if is_delta_message(data) and is_sign(data.delta_parameter):
             if not getattr(self._algorithm, "accepts_sign_messages", False):
                 data.delta_parameter = densify_sign_parameter(data.delta_parameter)
+        # and for ``lowrank.LowRankDelta`` values (factor pairs) and ``accepts_lowrank_messages``
+        # (LowRankFedAVGAlgorithm folds the factors themselves)
+        if is_delta_message(data) and is_lowrank(data.delta_parameter):
+            if not getattr(self._algorithm, "accepts_lowrank_messages", False):
+                data.delta_parameter = densify_lowrank_parameter(data.delta_parameter)
         # ``secagg.MaskedDelta`` values cannot be densified: one client's words are noise, and only
         # an algorithm with ``accepts_masked_messages`` (SecAggFedAVGAlgorithm) can remove the masks
         if is_delta_message(data) and is_masked(data.delta_parameter):

@@ -169,7 +169,10 @@ int32_t fedavg_build_flags(void);
  * lane owns), "secagg_loads" (clients whose vectors a lane has in flight), "secagg_split" (seed
  * entries from which the four waves of a workgroup share one tile and the seed entries, and the
  * clients, between them), "secagg_threads" and "secagg_max_seeds" of fedavg_secagg_mask and
- * fedavg_secagg_unmask: none of them enters the result.
+ * fedavg_secagg_unmask: none of them enters the result;
+ * "lowrank_tm" and "lowrank_tn" (rows and columns of a workgroup's output tile), "lowrank_kstep"
+ * (slots of K = clients * rank staged per step), "lowrank_threads", "lowrank_max_rank" and
+ * "lowrank_max_clients" of fedavg_lowrank_aggregate_delta.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -1114,6 +1117,40 @@ int32_t fedavg_secagg_unmask(fedavg_ctx* ctx, const void* const* client_ptrs /* 
                              int32_t frac_bits, double total_weight,
                              const double* const* base_ptrs /* [T], device fp64, or NULL */,
                              void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
+
+/*
+ * FedAvg over low-rank deltas against the fp64 base (the cached global model) in one launch. Segment t
+ * of the context's layout is a matrix of rows[t] rows and n_t = numel_t / rows[t] columns, row-major;
+ * client c sends its delta as two factors of one dtype (FEDAVG_F32 / F16 / BF16 / F64), each aligned to
+ * its element: left_ptrs[c * T + t] is L_c, [rows[t] x ranks[t]] row-major, right_ptrs[c * T + t] is
+ * R_c, [ranks[t] x n_t] row-major (structured low-rank updates: Konecny et al. 2016; PowerSGD: Vogels
+ * et al. 2019). Not an algorithm of the reference: the contract is DESIGN.md §5aa, restated
+ * independently in tests/lowrank_reference.py. Per element (i, e) of segment t, with r = ranks[t]:
+ *   a_c[i][j] = w_c * L_c[i][j]       the factor converted exactly to fp64, the product rounded once;
+ *   S = sum over c < num_clients, j < r of a_c[i][j] * R_c[j][e], summed by the fp64 matrix
+ *       instruction (v_mfma_f64_16x16x4_f64): the product is fused into the sum; the slots
+ *       k = c * r + j go in ascending order four to an instruction, inside one instruction the order
+ *       is the hardware's; the slots that pad the last instruction are +0.0 * +0.0;
+ *   out = b + S / divisor              two separately rounded fp64 operations, b = base_ptrs[t][i * n_t + e];
+ * an fp32 output is that value rounded to nearest even. This is the rule's own contract, not the bit
+ * pattern of fedavg_aggregate_delta on the densified deltas: the two agree bit for bit only where
+ * every operation is exact. The result is the same bits on every run and depends on the layout, the
+ * client order and the ranks alone. FEDAVG_FLAG_INPUT_NAN is latched for a NaN in a factor or the
+ * base, FEDAVG_FLAG_ACC_NAN for a NaN S (0 * inf, inf - inf), FEDAVG_FLAG_RESULT_NAN for a NaN output.
+ * The accumulator is not touched; nothing outside the outputs is written; no atomics. Asynchronous on
+ * `stream`. Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype or out_dtype; a NULL table or
+ * entry; num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS; a non-finite weight; a divisor that is not
+ * finite and > 0; rows[t] < 1 or not a divisor of numel_t; ranks[t] outside 1 ..
+ * FEDAVG_LOWRANK_MAX_RANK; a misaligned factor, base or output; out == base), FEDAVG_ERR_STATE (an
+ * open dynamic wave).
+ */
+#define FEDAVG_LOWRANK_MAX_RANK 16
+int32_t fedavg_lowrank_aggregate_delta(fedavg_ctx* ctx, const void* const* left_ptrs /* [n][T], device */,
+                                       const void* const* right_ptrs /* [n][T], device */, int32_t dtype,
+                                       const int32_t* rows /* [T], host */, const int32_t* ranks /* [T], host */,
+                                       const double* weights /* [n], host */, int32_t num_clients, double divisor,
+                                       const double* const* base_ptrs /* [T], device fp64 */,
+                                       void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
