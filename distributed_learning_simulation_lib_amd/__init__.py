@@ -22,6 +22,7 @@ from .algorithm import (
     GraphTopologyAlgorithm,
     KrumFedAVGAlgorithm,
     LowRankFedAVGAlgorithm,
+    MXFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
     SecAggFedAVGAlgorithm,
@@ -57,6 +58,7 @@ from .message import (
     ParameterMessageBase,
     get_message_size,
 )
+from .mx import MXDelta, MXEndpoint, MXErrorFeedback, mx_compress, mx_compress_parameter
 from .quantized import (
     BroadcastDequantizer,
     BroadcastQuantizer,
@@ -95,6 +97,10 @@ __all__ = [
     "LowRankEndpoint",
     "LowRankErrorFeedback",
     "LowRankFedAVGAlgorithm",
+    "MXDelta",
+    "MXEndpoint",
+    "MXErrorFeedback",
+    "MXFedAVGAlgorithm",
     "Message",
     "ModelLayout",
     "ModelParameter",
@@ -126,6 +132,8 @@ __all__ = [
     "get_message_size",
     "lowrank_compress",
     "lowrank_compress_parameter",
+    "mx_compress",
+    "mx_compress_parameter",
     "normal_stream",
     "philox_uniforms",
     "secagg_mask_parameter",
@@ -319,6 +327,20 @@ def _register_builtin() -> None:
                 client_cls=None,  # type: ignore[arg-type]
                 server_cls=AggregationServer,
                 algorithm_cls=LowRankFedAVGAlgorithm,
+                **endpoint,
+            )
+    # FedAvg over MX block-scaled deltas (FP8 / FP4 codes under E8M0 block scales), folded from the codes,
+    # and the same with workers that compress their diffs before sending (MXFP8 with error feedback unless
+    # the caller binds fmt="mxfp4" through the endpoint's keyword arguments)
+    for name, endpoint in (("fed_avg_mx", {}), ("fed_avg_mx_ef", {"client_endpoint_cls": MXEndpoint})):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=MXFedAVGAlgorithm,
                 **endpoint,
             )
     # FedAvg under secure aggregation: the unmasking rule behind the masking endpoint. The session seed has no

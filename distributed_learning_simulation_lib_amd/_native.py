@@ -19,6 +19,7 @@ F32, F16, BF16, F64 = 0, 1, 2, 3
 QSGD_F32, QSGD_F64 = 4, 5  # quantised records (quantized.py)
 NNADQ_F32, NNADQ_F64 = 6, 7
 RECORD_CODES = (QSGD_F32, QSGD_F64, NNADQ_F32, NNADQ_F64)
+MXFP8, MXFP4 = 8, 9  # FEDAVG_MXFP8 / FEDAVG_MXFP4: the formats of fedavg_mx_compress and fedavg_mx_aggregate_delta
 # enum fedavg_status
 OK = 0
 ERR_NAN_INPUT = 1
@@ -193,6 +194,12 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_lowrank_aggregate_delta": (
         c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, _PD, c_int32, c_double, _PP, _PP, c_int32,
                   c_void_p]),
+    # MX block-scaled FP8 / FP4 compression with error feedback and its fold (mx_kernels.hip); tables as raw addresses
+    "fedavg_mx_compress": (
+        c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                  c_void_p]),
+    "fedavg_mx_aggregate_delta": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_int32, _PD, c_int32, c_double, _PP, _PP, c_int32, c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

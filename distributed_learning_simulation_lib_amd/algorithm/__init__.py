@@ -11,6 +11,7 @@ from .graph_embedding_algorithm import GraphNodeEmbeddingPassingAlgorithm
 from .graph_topology_algorithm import GraphTopologyAlgorithm
 from .krum_aggregation_algorithm import KrumFedAVGAlgorithm
 from .lowrank_fed_avg_algorithm import LowRankFedAVGAlgorithm
+from .mx_fed_avg_algorithm import MXFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
 from .secagg_fed_avg_algorithm import SecAggFedAVGAlgorithm
@@ -22,6 +23,6 @@ from .sparse_fed_avg_algorithm import SparseFedAVGAlgorithm
 __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgorithm", "CompositeAggregationAlgorithm",
            "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "FoolsGoldFedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
-           "LowRankFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
+           "LowRankFedAVGAlgorithm", "MXFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
            "RobustFedAVGAlgorithm", "SecAggFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
            "SparseFedAVGAlgorithm"]

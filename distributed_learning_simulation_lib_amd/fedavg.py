@@ -38,6 +38,8 @@ from .rules import (  # noqa: F401 - re-exported: ``from ...fedavg import krum_s
     trust_coefficients,
 )
 from .lowrank import LowRankDelta
+from .mx import FORMATS as MX_FORMATS
+from .mx import MXDelta, code_bytes
 from .sign import SignDelta, bit_bytes
 from .sparse import SparseDelta
 
@@ -445,6 +447,39 @@ class SignBitTable:
                     raise ValueError(f"client {i}, tensor {t}: a contiguous sign delta of {numel} elements on "
                                      f"{device} is required")
                 self.bptr[i * T + t] = d.bits.data_ptr()
+        self.num_clients = n
+        self.layout = layout
+        self.device = device
+        self._keep = [list(row) for row in rows]
+
+
+class MXTable:
+    """Rows of mx deltas as the C-ABI arrays of ``fedavg_mx_aggregate_delta``: ``rows[i][t]`` is client
+    ``i``'s ``MXDelta`` of segment ``t`` of ``layout`` on ``device``, all of one format (built once,
+    reusable across calls; it keeps the tensors alive)."""
+
+    def __init__(self, rows: Sequence[Sequence[MXDelta]], layout: ModelLayout, device: torch.device) -> None:
+        n, T = len(rows), layout.num_segments
+        formats = set()
+        self.cptr = np.zeros(n * T, dtype=np.uint64)
+        self.sptr = np.zeros(n * T, dtype=np.uint64)
+        for i, row in enumerate(rows):
+            if len(row) != T:
+                raise ValueError(f"client {i}: one mx delta per segment is required")
+            for t, (d, numel) in enumerate(zip(row, layout.numels)):
+                if not isinstance(d, MXDelta):
+                    raise TypeError(f"client {i}, tensor {t}: an MXDelta is required, not {type(d).__name__}")
+                if d.numel != numel or d.codes.device != device or d.scales.device != device \
+                        or not d.codes.is_contiguous() or not d.scales.is_contiguous():
+                    raise ValueError(f"client {i}, tensor {t}: a contiguous mx delta of {numel} elements on "
+                                     f"{device} is required")
+                formats.add(d.fmt)
+                self.cptr[i * T + t] = d.codes.data_ptr()
+                self.sptr[i * T + t] = d.scales.data_ptr()
+        if len(formats) > 1:
+            raise ValueError(f"the mx deltas of one call share one format, not {sorted(formats)}")
+        self.fmt = formats.pop() if formats else "mxfp8"
+        self.dtype = torch.float64  # what the shared refusals ask of a table: no records
         self.num_clients = n
         self.layout = layout
         self.device = device
@@ -1351,6 +1386,84 @@ class FedAvgContext:
         _native.check(
             self._lib.fedavg_sign_aggregate_delta(
                 self._h, table.bptr.ctypes.data, table.sptr.ctypes.data, dtype_code(table.dtype),
+                w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
+            )
+        )
+
+    def mx_compress(self, deltas: Sequence[torch.Tensor], errors: Sequence[torch.Tensor | None] | None,
+                    codes: Sequence[torch.Tensor], scales: Sequence[torch.Tensor],
+                    residuals: Sequence[torch.Tensor], fmt: str = "mxfp8") -> None:
+        """MX block-scaled compression with error feedback of ``deltas`` (non-empty contiguous tensors
+        of one floating dtype on the context's device, of any sizes: the context's layout plays no
+        part) in one launch (``fedavg_mx_compress``): per block of 32 elements of
+        ``deltas[t] + errors[t]`` (``errors`` or an entry of it may be ``None``: no residual yet)
+        tensor ``t`` sends one E8M0 byte in ``scales[t]`` (uint8, ``ceil(numel / 32)`` bytes) and one
+        FP8 E4M3 (``fmt="mxfp8"``) or FP4 E2M1 (``"mxfp4"``) code per element in ``codes[t]`` (uint8,
+        ``mx.code_bytes(numel, fmt)`` bytes, 16-byte aligned), and leaves what it did not send in
+        ``residuals[t]``, which may be ``errors[t]`` or ``deltas[t]`` itself. Asynchronous; a
+        non-finite element latches the input flag (``flags()``)."""
+        T = len(deltas)
+        if fmt not in MX_FORMATS:
+            raise ValueError(f"the format is one of {sorted(MX_FORMATS)}, not {fmt!r}")
+        if T == 0 or not (len(codes) == len(scales) == len(residuals) == T) or (
+                errors is not None and len(errors) != T):
+            raise ValueError("one code, scale and residual tensor per delta and at least one delta are required")
+        dt = deltas[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the mx step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        ns = [x.numel() for x in deltas]
+        nc, nb = [code_bytes(n, fmt) for n in ns], [(n + 31) // 32 for n in ns]
+        groups = (("error", errors or (), dt, ns), ("code", codes, torch.uint8, nc), ("scale", scales, torch.uint8, nb),
+                  ("residual", residuals, dt, ns))
+        t, fault = _first(T, self._first_unfit(deltas, dt), next((t for t, n in enumerate(ns) if n == 0), T),
+                          *[self._first_unfit(g, dty, sizes) if g else T for _, g, dty, sizes in groups])
+        if fault == 0:
+            raise self._flat_refusal("delta", t, dt)
+        if fault == 1:
+            raise ValueError(f"delta {t}: an empty tensor has no codes and no scales, and is the caller's")
+        if fault >= 2:
+            what, _, dty, sizes = groups[fault - 2]
+            raise self._flat_refusal(what, t, dty, sizes[t])
+        xptr, cptr, sptr, rptr = (_addresses(deltas, ns), _addresses(codes, nc), _addresses(scales, nb),
+                                  _addresses(residuals, ns))
+        eptr = None if errors is None else _addresses(errors, ns)
+        ns = np.array(ns, dtype=np.int64)
+        _native.check(
+            self._lib.fedavg_mx_compress(
+                self._h, DTYPE_CODES[dt], MX_FORMATS[fmt], xptr.ctypes.data,
+                None if eptr is None else eptr.ctypes.data, ns.ctypes.data, T, cptr.ctypes.data, sptr.ctypes.data,
+                rptr.ctypes.data, self.stream,
+            )
+        )
+
+    def mx_aggregate_delta(self, rows: Sequence[Sequence[MXDelta]] | MXTable, weights: Sequence[float],
+                           divisor: float, base: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
+                           out_dtype: torch.dtype = torch.float64) -> None:
+        """FedAvg of mx deltas against ``base`` in one launch (``fedavg_mx_aggregate_delta``,
+        DESIGN.md §5ab): ``outs[t][e] = (sum_i (base[t][e] + d_i[e]) * w_i) / divisor`` with ``d_i[e]``
+        client ``i``'s ``code_value * 2^(s - 127)``, exact in fp64 — bit for bit the reference's
+        ``restore()`` + ``FedAVGAlgorithm`` on the densified deltas, and ``aggregate_delta`` on them.
+        ``rows[i][t]`` is client ``i``'s ``MXDelta`` of segment ``t`` on the context's device, all of
+        one format (or an ``MXTable`` built from such rows once); codes and scale bytes are read on
+        the device as they are. ``base`` is one contiguous fp64 tensor per segment, ``outs`` one
+        contiguous ``out_dtype`` tensor per segment, none of them its base's own storage. The
+        accumulator is not touched; the NaN flags are the caller's to read (``raise_on_nan``).
+        Refused before any launch: no clients, more than 1024, a delta that does not match its
+        segment, mixed formats, a code buffer that is not 16-byte aligned, a non-finite weight, a
+        divisor that is not finite and > 0, a base or an output that does not match, an output that
+        is its base."""
+        ocode = out_code(out_dtype)
+        table = rows if isinstance(rows, MXTable) else MXTable(rows, self.layout, self.device)
+        if table.layout != self.layout or table.device != self.device:
+            raise ValueError("the mx table was built for another layout or device")
+        self._refuse_before_table(table, table.dtype, "the mx fold", "s", _native.POINT_MAX_CLIENTS)
+        n = table.num_clients
+        w = _client_scalars(weights, n, "weight")
+        divisor = _divisor(divisor)
+        zp, op = self._source_and_outputs("base", base, outs, out_dtype, "the mx fold is not in-place")
+        _native.check(
+            self._lib.fedavg_mx_aggregate_delta(
+                self._h, table.cptr.ctypes.data, table.sptr.ctypes.data, MX_FORMATS[table.fmt],
                 w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
             )
         )

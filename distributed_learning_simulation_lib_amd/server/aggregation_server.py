@@ -38,6 +38,8 @@ from ..quantized import dequantize_parameter, is_quantized
 from ..secagg import is_masked
 from ..lowrank import densify_parameter as densify_lowrank_parameter
 from ..lowrank import is_lowrank
+from ..mx import densify_parameter as densify_mx_parameter
+from ..mx import is_mx
 from ..sign import densify_parameter as densify_sign_parameter
 from ..sign import is_sign
 from ..sparse import densify_parameter, is_sparse
@@ -209,6 +211,11 @@ class AggregationServer:
         if is_delta_message(data) and is_lowrank(data.delta_parameter):
             if not getattr(self._algorithm, "accepts_lowrank_messages", False):
                 data.delta_parameter = densify_lowrank_parameter(data.delta_parameter)
+        # and for ``mx.MXDelta`` values (block-scaled FP8 / FP4 codes) and ``accepts_mx_messages``
+        # (MXFedAVGAlgorithm folds the codes and scale bytes themselves)
+        if is_delta_message(data) and is_mx(data.delta_parameter):
+            if not getattr(self._algorithm, "accepts_mx_messages", False):
+                data.delta_parameter = densify_mx_parameter(data.delta_parameter)
         # ``secagg.MaskedDelta`` values cannot be densified: one client's words are noise, and only
         # an algorithm with ``accepts_masked_messages`` (SecAggFedAVGAlgorithm) can remove the masks
         if is_delta_message(data) and is_masked(data.delta_parameter):

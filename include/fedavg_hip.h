@@ -172,7 +172,11 @@ int32_t fedavg_build_flags(void);
  * fedavg_secagg_unmask: none of them enters the result;
  * "lowrank_tm" and "lowrank_tn" (rows and columns of a workgroup's output tile), "lowrank_kstep"
  * (slots of K = clients * rank staged per step), "lowrank_threads", "lowrank_max_rank" and
- * "lowrank_max_clients" of fedavg_lowrank_aggregate_delta.
+ * "lowrank_max_clients" of fedavg_lowrank_aggregate_delta;
+ * "mx_block" (32: elements that share a scale byte), "mx_tile" (elements per workgroup of
+ * fedavg_mx_compress and fedavg_mx_aggregate_delta), "mx_threads" (lanes of an encoder workgroup and
+ * of an FP8 fold workgroup; an FP4 fold workgroup has half of them), "mx_batch" (clients whose scale
+ * bytes the fold stages at a time) and "mx_max_clients": none of them enters the result.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -1151,6 +1155,72 @@ int32_t fedavg_lowrank_aggregate_delta(fedavg_ctx* ctx, const void* const* left_
                                        const double* weights /* [n], host */, int32_t num_clients, double divisor,
                                        const double* const* base_ptrs /* [T], device fp64 */,
                                        void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
+
+/*
+ * OCP Microscaling (MX) client updates (OCP Microscaling Formats (MX) Specification v1.0): a block of 32
+ * consecutive elements shares one E8M0 scale byte, each element is one FP8 E4M3 or FP4 E2M1 code.
+ * Format ids, beside the codec ids of enum fedavg_dtype: FEDAVG_MXFP8 and FEDAVG_MXFP4.
+ *   E4M3 (the "FN" form): bias 7, subnormals, largest finite value 448, S.1111.111 is NaN, no infinity.
+ *   E2M1: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, no NaN, no infinity.
+ *   scale byte s (E8M0): 0 .. 254 stands for 2^(s - 127), 255 is NaN.
+ * Payload of a tensor of n elements, B = ceil(n / 32) blocks: `scales`, B bytes, aligned to the byte
+ * only; `codes`, 16-byte aligned, 32 B bytes for MXFP8 (element e is byte e) or 16 B bytes for MXFP4
+ * (element e is in byte e / 2, the even element in the low nibble). The code positions past n in the
+ * last block are written as code 0 and ignored by every reader.
+ * Element value: v = code_value * 2^(s - 127), exact: every such product is an fp64 normal number (or
+ * a zero that keeps its sign).
+ *
+ * fedavg_mx_compress, the client step over num_tensors device tensors of one dtype (FEDAVG_F32 / F16 /
+ * BF16 / F64), tensor t of numels[t] (host, 1 .. 2^31 - 1) elements, with error feedback. Per tensor
+ * and block, with emax = 8 (E4M3) or 2 (E2M1):
+ *   total[e] = delta[e] + error[e], rounded once to nearest even into the dtype; without an error
+ *              total[e] is delta[e] bit for bit.
+ *   amax     = the largest |total[e]| of the block's real elements;
+ *   E        = floor(log2 amax) - emax clamped to [-127, 127], or -127 for amax == 0;  s = E + 127;
+ *   q[e]     = total[e] / 2^E, exact;
+ *   code[e]  = q[e] rounded once to nearest, ties to even, in the element format, subnormals included;
+ *              |q| above the largest finite value saturates to it; the sign bit of total[e] is kept
+ *              (-0.0 sends the negative-zero code);
+ *   sent[e]  = the element value rounded once into the dtype;
+ *   residual_ptrs[t][e] = total[e] - sent[e], rounded once to nearest even into the dtype.
+ * residual_ptrs[t] may be error_ptrs[t] or delta_ptrs[t] (every element is read and then written by
+ * the same lane); no other overlap is allowed. Nothing outside the outputs is written. One launch
+ * whatever num_tensors is; no atomics, no host round trip: asynchronous on `stream`. The result
+ * depends on the inputs alone. A non-finite total[e] latches FEDAVG_FLAG_INPUT_NAN (the outputs are
+ * then unspecified but stay inside their buffers). The accumulator and its state are not touched.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype or format; a NULL table other than
+ * error_ptrs; num_tensors < 1 or > 2^20; numels[t] < 1 or > 2^31 - 1; a NULL delta, residual, code or
+ * scale buffer; a delta, error or residual not aligned to its element; a code buffer not 16-byte
+ * aligned), FEDAVG_ERR_STATE (an open dynamic wave).
+ *
+ * fedavg_mx_aggregate_delta, FedAvg over MX deltas against the fp64 base (the cached global model) in
+ * one launch: per element e of segment t, with b = base_ptrs[t][e] and v_i the element value of client
+ * i's payload code_ptrs[i * T + t], scale_ptrs[i * T + t],
+ *   d_i = v_i (exact);  x_i = b + d_i;  p_i = x_i * w_i;
+ *   acc = p_0, then acc = acc + p_i in table order;  out[e] = acc / divisor
+ * each a separately rounded fp64 operation (no FMA, no leading 0 +; fp32 out: that result rounded to
+ * nearest even). Bit for bit the reference's restore() followed by FedAVGAlgorithm on the densified
+ * deltas, and fedavg_aggregate_delta on them. All clients of a call share `format`; out_dtype is
+ * FEDAVG_F32 or FEDAVG_F64. FEDAVG_FLAG_INPUT_NAN for a NaN x_i (scale byte 255, an E4M3 NaN code, a
+ * NaN base), FEDAVG_FLAG_ACC_NAN, FEDAVG_FLAG_RESULT_NAN. The accumulator is not touched. No atomics.
+ * Asynchronous on `stream`. Refused before any launch: FEDAVG_ERR_INVALID (a bad format or out_dtype,
+ * NULL tables or entries, num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS, a non-finite weight, a
+ * divisor that is not finite and > 0, a misaligned base or output, out == base, a code buffer that is
+ * not 16-byte aligned), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_MXFP8 8
+#define FEDAVG_MXFP4 9
+int32_t fedavg_mx_compress(fedavg_ctx* ctx, int32_t dtype, int32_t format,
+                           const void* const* delta_ptrs /* [T], device */,
+                           const void* const* error_ptrs /* [T], device, or NULL; entries may be NULL */,
+                           const int64_t* numels /* [T], host */, int32_t num_tensors,
+                           void* const* code_ptrs /* [T], device */, void* const* scale_ptrs /* [T], device */,
+                           void* const* residual_ptrs /* [T], device */, void* stream);
+int32_t fedavg_mx_aggregate_delta(fedavg_ctx* ctx, const void* const* code_ptrs /* [n][T], device */,
+                                  const void* const* scale_ptrs /* [n][T], device */, int32_t format,
+                                  const double* weights /* [n], host */, int32_t num_clients, double divisor,
+                                  const double* const* base_ptrs /* [T], device fp64 */,
+                                  void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
