@@ -44,13 +44,13 @@ GRAM_MAX_CLIENTS = 256  # FEDAVG_GRAM_MAX_CLIENTS: fedavg_gram_about_point
 POINT_MAX_CLIENTS = 1024  # FEDAVG_POINT_MAX_CLIENTS: fedavg_sqdist_to_point, fedavg_fold_about_point,
 # fedavg_moments_about_point, fedavg_server_opt_step, fedavg_sparse_aggregate_delta, fedavg_sign_aggregate_delta,
 # fedavg_sign_majority_vote, fedavg_lowrank_aggregate_delta
-LOWRANK_MAX_RANK = 16  # FEDAVG_LOWRANK_MAX_RANK: fedavg_lowrank_aggregate_delta
+LOWRANK_MAX_RANK = 16  # FEDAVG_LOWRANK_MAX_RANK: fedavg_lowrank_aggregate_delta, fedavg_lowrank_compress
 SECAGG_MAX_CLIENTS = 1024  # FEDAVG_SECAGG_MAX_CLIENTS: fedavg_secagg_unmask
 ROUTE_MAX_SOURCES = 1024  # fedavg_route_rows
 ROUTE_MAX_NODE_SPACE = 1 << 28
 ROUTE_ERR_DUPLICATE, ROUTE_ERR_ORDER, ROUTE_ERR_RANGE = 1, 2, 4  # bits of fedavg_route_errors
 OPT_AVGM, OPT_ADAGRAD, OPT_YOGI, OPT_ADAM = 0, 1, 2, 3  # FEDAVG_OPT_*: fedavg_server_opt_step modes
-ABI_VERSION = 1
+ABI_VERSION = 2
 ACC_ALIGN = 32  # FEDAVG_ACC_ALIGN: accumulator segments start at multiples of 32 elements
 BUILD_ABLATE_EPILOGUE = 0x1
 BUILD_ABLATE_QSGD = 0x2
@@ -194,6 +194,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "fedavg_lowrank_aggregate_delta": (
         c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, _PD, c_int32, c_double, _PP, _PP, c_int32,
                   c_void_p]),
+    # the low-rank client step (lowrank_kernels.hip); tables as raw addresses
+    "fedavg_lowrank_compress": (
+        c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                  c_void_p, c_void_p, c_void_p, c_void_p]),
     # MX block-scaled FP8 / FP4 compression with error feedback and its fold (mx_kernels.hip); tables as raw addresses
     "fedavg_mx_compress": (
         c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,

@@ -1436,6 +1436,64 @@ class FedAvgContext:
             )
         )
 
+    def lowrank_compress(self, deltas: Sequence[torch.Tensor], errors: Sequence[torch.Tensor | None] | None,
+                         starts: Sequence[torch.Tensor], lefts: Sequence[torch.Tensor],
+                         rights: Sequence[torch.Tensor], residuals: Sequence[torch.Tensor]) -> None:
+        """One power-iteration step with error feedback per tensor of ``deltas`` (contiguous tensors
+        of at least 2 dimensions and one floating dtype on the context's device, of any shapes: the
+        context's layout plays no part) in five launches (``fedavg_lowrank_compress``, DESIGN.md
+        §5ac). Tensor ``t`` is the ``[m, n]`` matrix of its first dimension against the rest and
+        ``starts[t]`` the ``[r, n]`` start of the iteration, in the deltas' dtype (the ``right`` of
+        the round before) or float64; with ``M = deltas[t] + errors[t]`` in float64 (``errors`` or an
+        entry of it may be ``None``: no residual yet) ``lefts[t]`` receives the orthonormalised
+        ``M startsᵀ`` as ``[m, r]``, ``rights[t]`` ``leftᵀ M`` as ``[r, n]`` and ``residuals[t]``
+        ``M - left right`` of the rounded factors. No output may be an input's storage.
+        Asynchronous; a non-finite element latches the input flag (``flags()``)."""
+        T = len(deltas)
+        if T == 0 or not (len(starts) == len(lefts) == len(rights) == len(residuals) == T) or (
+                errors is not None and len(errors) != T):
+            raise ValueError("one start, left, right and residual tensor per delta and at least one delta are required")
+        dt = deltas[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the low-rank step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        t = self._first_unfit(deltas, dt)
+        if t < T:
+            raise self._flat_refusal("delta", t, dt)
+        ms, ns, rs = [], [], []
+        for t, (d, q) in enumerate(zip(deltas, starts)):
+            if d.dim() < 2 or not 0 < d.numel() <= 0x7FFFFFFF:
+                raise ValueError(f"delta {t}: a tensor of at least 2 dimensions and 1 .. 2^31 - 1 elements is required")
+            m = int(d.shape[0])
+            n = d.numel() // m
+            r = int(q.shape[0]) if q.dim() == 2 else 0
+            if not 1 <= r <= _native.LOWRANK_MAX_RANK or q.shape[1] != n:
+                raise ValueError(f"start {t}: [r, {n}] with r in 1 .. {_native.LOWRANK_MAX_RANK} is required, not "
+                                 f"{tuple(q.shape)}")
+            if q.dtype not in (dt, torch.float64) or q.device != self.device or not q.is_contiguous():
+                raise ValueError(f"start {t}: a contiguous {dt} or torch.float64 tensor on {self.device} is required")
+            if r * (m + n) >= m * n:
+                raise ValueError(f"delta {t}: rank {r} factors would not make a [{m}, {n}] matrix smaller")
+            ms.append(m), ns.append(n), rs.append(r)
+        mn, mr, rn = ([m * n for m, n in zip(ms, ns)], [m * r for m, r in zip(ms, rs)],
+                      [r * n for r, n in zip(rs, ns)])
+        groups = (("error", errors or (), mn), ("left", lefts, mr), ("right", rights, rn), ("residual", residuals, mn))
+        t, fault = _first(T, *[self._first_unfit(g, dt, sizes) if g else T for _, g, sizes in groups])
+        if fault >= 0:
+            what, _, sizes = groups[fault]
+            raise self._flat_refusal(what, t, dt, sizes[t])
+        xptr, qptr, lptr, rptr, sptr = (_addresses(deltas, mn), _addresses(starts, rn), _addresses(lefts, mr),
+                                        _addresses(rights, rn), _addresses(residuals, mn))
+        eptr = None if errors is None else _addresses(errors, mn)
+        qcodes = np.array([DTYPE_CODES[q.dtype] for q in starts], dtype=np.int32)
+        ms, ns, rs = (np.array(x, dtype=np.int32) for x in (ms, ns, rs))
+        _native.check(
+            self._lib.fedavg_lowrank_compress(
+                self._h, DTYPE_CODES[dt], xptr.ctypes.data, None if eptr is None else eptr.ctypes.data,
+                qptr.ctypes.data, qcodes.ctypes.data, ms.ctypes.data, ns.ctypes.data, rs.ctypes.data, T,
+                lptr.ctypes.data, rptr.ctypes.data, sptr.ctypes.data, self.stream,
+            )
+        )
+
     def mx_aggregate_delta(self, rows: Sequence[Sequence[MXDelta]] | MXTable, weights: Sequence[float],
                            divisor: float, base: Sequence[torch.Tensor], outs: Sequence[torch.Tensor],
                            out_dtype: torch.dtype = torch.float64) -> None:

@@ -8,9 +8,11 @@ dimension against the rest. ``LowRankDelta`` is what travels: a value of
 ``DeltaParameterMessage.delta_parameter[name]`` of ``r (m + n)`` values instead of ``m n``.
 ``LowRankFedAVGAlgorithm`` folds the factors as they are (``fedavg_lowrank_aggregate_delta``, DESIGN.md
 §5aa: the round's sum is one product per tensor on the fp64 matrix unit), every other algorithm gets
-``to_dense()`` from the server. The client step, one power-iteration step, is plain torch here: the
-server fold is the hot path. ``LowRankErrorFeedback`` keeps the residuals and the warm-start factors
-and ``LowRankEndpoint`` puts the step in front of a client endpoint.
+``to_dense()`` from the server. The client step, one power-iteration step, is
+``fedavg_lowrank_compress`` on a GPU (one call and five launches for a whole diff, the
+products on the fp64 matrix unit, no host round trip) and a torch composition of the same contract on
+the host, which is also the kernel's oracle. ``LowRankErrorFeedback`` keeps the residuals and the
+warm-start factors and ``LowRankEndpoint`` puts the step in front of a client endpoint.
 """
 
 from __future__ import annotations
@@ -23,6 +25,7 @@ from typing import Any
 
 import torch
 
+from . import _native
 from ._native import LOWRANK_MAX_RANK
 from .message import is_delta_message
 from .sparse import INT32_MAX, VALUE_DTYPES
@@ -118,9 +121,82 @@ def _orthonormalise(P: torch.Tensor) -> torch.Tensor:
     return torch.stack(cols, dim=1)
 
 
+def _shape(delta: torch.Tensor, rank: int) -> tuple[int, int] | None:
+    """``(m, n)`` of a tensor the factors make smaller, ``None`` for one that travels dense."""
+    if delta.dim() < 2:
+        return None
+    m, n = int(delta.shape[0]), math.prod(delta.shape[1:])
+    return None if rank * (m + n) >= m * n else (m, n)
+
+
+def _check_start(right_prev: torch.Tensor | None, m: int, n: int, rank: int) -> None:
+    if right_prev is not None and tuple(right_prev.shape) != (rank, n):
+        raise ValueError(f"the warm start of a [{m}, {n}] matrix at rank {rank} is [{rank}, {n}], not "
+                         f"{tuple(right_prev.shape)}")
+
+
+def _first_start(rank: int, n: int) -> torch.Tensor:
+    """The start of a tensor's first round: fixed by ``n`` alone, made on the host."""
+    return torch.randn(rank, n, dtype=torch.float64, generator=torch.Generator().manual_seed(n))
+
+
+def _for_kernel(delta: torch.Tensor, rank: int, error: torch.Tensor | None) -> bool:
+    """The kernel takes a floating tensor on a GPU that the factors make smaller, of at most 2^31 - 1
+    elements, with a residual (if any) of its own shape, dtype and device; the torch composition
+    takes everything else."""
+    return (delta.device.type == "cuda" and delta.dtype in VALUE_DTYPES and _shape(delta, rank) is not None
+            and delta.numel() <= INT32_MAX
+            and (error is None or (error.shape == delta.shape and error.dtype == delta.dtype
+                                   and error.device == delta.device)))
+
+
+@torch.no_grad()
+def _lowrank_compress_kernel(deltas: list[torch.Tensor], rank: int, starts: list[torch.Tensor | None],
+                             errors: list[torch.Tensor | None]) -> list[tuple[LowRankDelta, torch.Tensor]]:
+    """One ``fedavg_lowrank_compress`` call over compressible tensors of one dtype on one GPU."""
+    from .sign import _context  # the layout-free context of a device, shared with the sign step
+
+    device, dt = deltas[0].device, deltas[0].dtype
+    mats, qs = [], []
+    for d, q in zip(deltas, starts):
+        m, n = _shape(d, rank)
+        _check_start(q, m, n, rank)
+        mats.append(d.detach().contiguous())
+        if q is None:
+            q = _first_start(rank, n).to(device)
+        elif q.device != device or q.dtype not in (dt, torch.float64):
+            q = q.detach().to(device=device, dtype=torch.float64)
+        qs.append(q.detach().contiguous())
+    errs = [None if e is None else e.detach().contiguous() for e in errors]
+    lefts = [torch.empty(d.shape[0], rank, dtype=dt, device=device) for d in mats]
+    rights = [torch.empty(rank, q.shape[1], dtype=dt, device=device) for q in qs]
+    res = [torch.empty_like(d) for d in mats]
+    ctx = _context(device)
+    ctx.lowrank_compress(mats, errs, qs, lefts, rights, res)
+    if ctx.flags() & _native.FLAG_INPUT_NAN:  # waits for the stream
+        ctx.reset()  # the flag is sticky until reset: the context stays usable
+        raise ValueError("lowrank_compress: a non-finite element")
+    return [(LowRankDelta(l, r, tuple(d.shape)), e.view(d.shape)) for d, l, r, e in zip(deltas, lefts, rights, res)]
+
+
 @torch.no_grad()
 def lowrank_compress(delta: torch.Tensor, rank: int, right_prev: torch.Tensor | None = None,
                      error: torch.Tensor | None = None) -> tuple[LowRankDelta | torch.Tensor, torch.Tensor]:
+    """One PowerSGD step (``_lowrank_compress_torch`` states it). A compressible floating tensor on a
+    GPU goes through ``fedavg_lowrank_compress``: the same contract at the kernel's
+    own summation order, the same bits on every run, and a non-finite element is a ``ValueError``.
+    Host tensors go through the torch composition."""
+    rank = _check_rank(rank)
+    if delta.dtype not in VALUE_DTYPES:
+        raise TypeError(f"low-rank compression takes fp32, fp16, bf16 and fp64 tensors, not {delta.dtype}")
+    if _for_kernel(delta, rank, error):
+        return _lowrank_compress_kernel([delta], rank, [right_prev], [error])[0]
+    return _lowrank_compress_torch(delta, rank, right_prev, error)
+
+
+@torch.no_grad()
+def _lowrank_compress_torch(delta: torch.Tensor, rank: int, right_prev: torch.Tensor | None = None,
+                            error: torch.Tensor | None = None) -> tuple[LowRankDelta | torch.Tensor, torch.Tensor]:
     """One PowerSGD step: ``M = delta + error`` as an ``[m, n]`` matrix, ``P = M Qᵀ`` with ``Q`` the
     ``right`` of the round before (``right_prev``; a fixed pseudo-random matrix without one),
     ``P`` orthonormalised by Gram–Schmidt, ``Q = Pᵀ M``; ``left = P`` and ``right = Q`` rounded into the
@@ -156,16 +232,30 @@ def lowrank_compress_parameter(delta: Mapping[str, torch.Tensor], rank: int,
                                error: Mapping[str, torch.Tensor] | None = None,
                                ) -> tuple[dict[str, LowRankDelta | torch.Tensor], dict[str, torch.Tensor]]:
     """``lowrank_compress`` per tensor of a parameter diff (a name that ``right_prev`` or ``error`` lacks
-    has no warm start or residual yet). Returns what is sent and the new residuals, both by name. A
+    has no warm start or residual yet). Returns what is sent and the new residuals, both by name. The
+    compressible tensors of one floating dtype on one GPU go through one ``fedavg_lowrank_compress``
+    call; host tensors, mixed dtypes and dicts spread over several devices go tensor by tensor. A
     non-floating tensor is a ``TypeError``."""
-    sent, residual = {}, {}
-    for name, value in delta.items():
+    rank = _check_rank(rank)
+    items = list(delta.items())
+    for name, value in items:
         if not isinstance(value, torch.Tensor) or value.dtype not in VALUE_DTYPES:
             kind = value.dtype if isinstance(value, torch.Tensor) else type(value).__name__
             raise TypeError(f"{name}: low-rank compression takes fp32, fp16, bf16 and fp64 tensors, not {kind}")
-        sent[name], residual[name] = lowrank_compress(value, rank, None if right_prev is None else right_prev.get(name),
-                                                      None if error is None else error.get(name))
-    return sent, residual
+    starts = [None if right_prev is None else right_prev.get(name) for name, _ in items]
+    errors = [None if error is None else error.get(name) for name, _ in items]
+    results: list[Any] = [None] * len(items)
+    fit = [k for k, ((_, v), e) in enumerate(zip(items, errors)) if _for_kernel(v, rank, e)]
+    if fit and len({items[k][1].device for k in fit}) == 1 and len({items[k][1].dtype for k in fit}) == 1:
+        done = _lowrank_compress_kernel([items[k][1] for k in fit], rank, [starts[k] for k in fit],
+                                        [errors[k] for k in fit])
+        for k, r in zip(fit, done):
+            results[k] = r
+    for k, ((_, v), q, e) in enumerate(zip(items, starts, errors)):
+        if results[k] is None:
+            results[k] = lowrank_compress(v, rank, q, e)
+    return ({name: r[0] for (name, _), r in zip(items, results)},
+            {name: r[1] for (name, _), r in zip(items, results)})
 
 
 class LowRankErrorFeedback:

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define FEDAVG_ABI_VERSION 1
+#define FEDAVG_ABI_VERSION 2
 
 /* element types */
 enum fedavg_dtype {
@@ -172,7 +172,10 @@ int32_t fedavg_build_flags(void);
  * fedavg_secagg_unmask: none of them enters the result;
  * "lowrank_tm" and "lowrank_tn" (rows and columns of a workgroup's output tile), "lowrank_kstep"
  * (slots of K = clients * rank staged per step), "lowrank_threads", "lowrank_max_rank" and
- * "lowrank_max_clients" of fedavg_lowrank_aggregate_delta;
+ * "lowrank_max_clients" of fedavg_lowrank_aggregate_delta; "lowrank_chunk_cols" (columns whose
+ * products one workgroup of P = M Q^T sums), "lowrank_chunk_rows" (rows one workgroup of R = P^^T M
+ * sums), "lowrank_ortho_lds_rows" (the most rows for which the orthonormaliser keeps P in LDS) and
+ * "lowrank_ortho_threads" of fedavg_lowrank_compress: the two chunk sizes enter its result;
  * "mx_block" (32: elements that share a scale byte), "mx_tile" (elements per workgroup of
  * fedavg_mx_compress and fedavg_mx_aggregate_delta), "mx_threads" (lanes of an encoder workgroup and
  * of an FP8 fold workgroup; an FP4 fold workgroup has half of them), "mx_batch" (clients whose scale
@@ -1155,6 +1158,45 @@ int32_t fedavg_lowrank_aggregate_delta(fedavg_ctx* ctx, const void* const* left_
                                        const double* weights /* [n], host */, int32_t num_clients, double divisor,
                                        const double* const* base_ptrs /* [T], device fp64 */,
                                        void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
+
+/*
+ * The client step of the low-rank format: one power-iteration step (PowerSGD, Vogels et al. 2019) with
+ * error feedback over num_tensors device tensors of one dtype T (FEDAVG_F32 / F16 / BF16 / F64), whatever
+ * the context's layout is. Tensor t is a row-major [rows[t] x cols[t]] matrix (m x n) at rank
+ * r = ranks[t]; q_ptrs[t] is the start Q, [r x n] row-major, of dtype q_dtypes[t]: T (the right factor
+ * of the round before) or FEDAVG_F64 (a first-round matrix). The contract is DESIGN.md §5ac:
+ *   M        = fl64(delta) + fl64(error)        (error_ptrs, or an entry of it, may be NULL: no residual yet)
+ *   P        = M Q^T                             [m x r], summed by v_mfma_f64_16x16x4_f64 in chunks of
+ *                                                "lowrank_chunk_cols" columns; the chunk sums are added in
+ *                                                ascending chunk order
+ *   P^       = the columns of P orthonormalised in ascending order: twice (the dot products against all
+ *              earlier columns, then their multiples subtracted in ascending order), then divided by the
+ *              norm; a column whose norm is exactly 0 stays 0
+ *   R        = P^^T M                            [r x n], in chunks of "lowrank_chunk_rows" rows, added in
+ *                                                ascending chunk order
+ *   left_ptrs[t] = round_T(P^), right_ptrs[t] = round_T(R), each rounded once to nearest even;
+ *   residual_ptrs[t] = round_T(M - fl64(left) fl64(right)), the product of the rounded factors summed by
+ *              the matrix instruction, the difference rounded once.
+ * Inside one matrix instruction and one workgroup reduction the order is fixed by the hardware and the
+ * kernel, not by the torch composition: the result is the same bits on every run and depends on the
+ * inputs and shapes alone, but it is not the bit pattern of lowrank._lowrank_compress_torch. Five
+ * launches whatever num_tensors is; no atomics; no host round trip: asynchronous on `stream`. Nothing
+ * outside the outputs and the module's workspace is written; no output may overlap an input. A
+ * non-finite element of delta + error or of Q latches FEDAVG_FLAG_INPUT_NAN (the outputs are then
+ * unspecified but stay inside their buffers). The accumulator and its state are not touched.
+ * Refused before any launch: FEDAVG_ERR_INVALID (a bad dtype; a NULL table other than error_ptrs;
+ * num_tensors < 1 or > 2^20; rows[t] < 1 or cols[t] < 1; more than 2^31 - 1 elements; ranks[t] outside
+ * 1 .. FEDAVG_LOWRANK_MAX_RANK; a tensor the factors would not make smaller, r (m + n) >= m n; a start
+ * dtype that is neither T nor FEDAVG_F64; a NULL delta, start, left, right or residual buffer; a buffer
+ * not aligned to its element), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+int32_t fedavg_lowrank_compress(fedavg_ctx* ctx, int32_t dtype, const void* const* delta_ptrs /* [T], device */,
+                                const void* const* error_ptrs /* [T], device, or NULL; entries may be NULL */,
+                                const void* const* q_ptrs /* [T], device */, const int32_t* q_dtypes /* [T], host */,
+                                const int32_t* rows /* [T], host */, const int32_t* cols /* [T], host */,
+                                const int32_t* ranks /* [T], host */, int32_t num_tensors,
+                                void* const* left_ptrs /* [T], device */, void* const* right_ptrs /* [T], device */,
+                                void* const* residual_ptrs /* [T], device */, void* stream);
 
 /*
  * OCP Microscaling (MX) client updates (OCP Microscaling Formats (MX) Specification v1.0): a block of 32

@@ -16,6 +16,8 @@ One JSON line goes to --out (default profiles/lowrank_lines.jsonl) with each rat
 operation model (N r m n fp64 multiply-adds per matrix) over the 78.6 TFLOP/s fp64 matrix peak and the
 byte model (the factors once, base and result) over the 8.0 TB/s HBM peak, and the share of the bound
 that applies. Not traced. No GPU, no number.
+
+``--leg compress`` times the client step instead (``compress_lines``) and appends its lines to --out.
 """
 
 from __future__ import annotations
@@ -59,13 +61,74 @@ def events(fn, device) -> float:
     return a.elapsed_time(b)
 
 
+def compress_lines(args, device) -> None:
+    """The client step: one client's ResNet-18 diff at rank 4, fp32 and fp64, with and without
+    residuals. (k) ``FedAvgContext.lowrank_compress`` over all compressible tensors into
+    preallocated outputs; (t) ``_lowrank_compress_torch`` per tensor on the same device tensors. The
+    byte model is delta (+ error) read three times and the residual written once. One JSON line
+    per case is appended to --out."""
+    from distributed_learning_simulation_lib_amd.lowrank import _lowrank_compress_torch, _shape
+    from distributed_learning_simulation_lib_amd.sign import _context
+
+    layout = resnet18_layout()
+    g = torch.Generator(device="cpu").manual_seed(1)
+    shapes = [s for s in layout.shapes if len(s) >= 2 and _shape(torch.empty(s, device="meta"), RANK) is not None]
+    ctx = _context(device)
+    for dtype in (torch.float32, torch.float64):
+        deltas = [(torch.randn(*s, generator=g) * 0.01).to(dtype).to(device) for s in shapes]
+        errors = [(torch.randn(*s, generator=g) * 0.001).to(dtype).to(device) for s in shapes]
+        starts = [torch.randn(RANK, d.numel() // d.shape[0], generator=g).to(dtype).to(device) for d in deltas]
+        lefts = [torch.empty(d.shape[0], RANK, dtype=dtype, device=device) for d in deltas]
+        rights = [torch.empty_like(q) for q in starts]
+        res = [torch.empty_like(d) for d in deltas]
+        for with_error in (False, True):
+            errs = errors if with_error else None
+
+            def k_call():
+                ctx.lowrank_compress(deltas, errs, starts, lefts, rights, res)
+
+            def t_call():
+                for i, d in enumerate(deltas):
+                    _lowrank_compress_torch(d, RANK, starts[i], errs[i] if errs else None)
+
+            legs = {"k": k_call, "t": t_call}
+            for _ in range(args.warmup):
+                for fn in legs.values():
+                    events(fn, device)
+            assert ctx.flags() == 0
+            ts: dict[str, list[float]] = {k: [] for k in legs}
+            for _ in range(args.runs):  # interleaved: drift hits every leg alike
+                for key, fn in legs.items():
+                    ts[key].append(events(fn, device))
+            sp = {k: spread(v) for k, v in ts.items()}
+            p = sum(d.numel() for d in deltas)
+            model_bytes = deltas[0].element_size() * p * (3 * (2 if with_error else 1) + 1)
+            line = {"what": "lowrank_compress", "case": f"resnet18_{str(dtype).split('.')[-1]}", "rank": RANK,
+                    "with_residuals": with_error, "tensors": len(deltas), "elements": p,
+                    "device": torch.cuda.get_device_name(device), "traced": False, "kernel_call": sp["k"],
+                    "torch_per_tensor": sp["t"], "ratio_torch_over_kernel": sp["t"]["median_ms"] / sp["k"]["median_ms"],
+                    "model_bytes": model_bytes, "bound_ms_bytes": model_bytes / HBM_PEAK_GBPS / 1e6,
+                    "share_of_byte_bound": model_bytes / HBM_PEAK_GBPS / 1e6 / sp["k"]["median_ms"],
+                    "launches": 5, **{k: _native.kernel_constant(k) for k in
+                                      ("lowrank_chunk_cols", "lowrank_chunk_rows", "lowrank_ortho_lds_rows")}}
+            print(json.dumps(line))
+            args.out.parent.mkdir(parents=True, exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--runs", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", type=Path, default=REPO / "profiles" / "lowrank_lines.jsonl")
+    ap.add_argument("--leg", choices=("fold", "compress"), default="fold",
+                    help="fold: the server round (rewrites --out); compress: the client step (appends to --out)")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
+    if args.leg == "compress":
+        compress_lines(args, device)
+        return
     layout = resnet18_layout()
     T = layout.num_segments
     low = [i for i, s in enumerate(layout.shapes) if len(s) >= 2]
