@@ -25,6 +25,7 @@ from .algorithm import (
     MXFedAVGAlgorithm,
     PersonalizedFedAVGAlgorithm,
     RobustFedAVGAlgorithm,
+    RotatedSignFedAVGAlgorithm,
     SecAggFedAVGAlgorithm,
     ServerOptFedAVGAlgorithm,
     SignFedAVGAlgorithm,
@@ -59,6 +60,13 @@ from .message import (
     get_message_size,
 )
 from .mx import MXDelta, MXEndpoint, MXErrorFeedback, mx_compress, mx_compress_parameter
+from .rotated import (
+    RotatedSignDelta,
+    RotatedSignEndpoint,
+    RotatedSignErrorFeedback,
+    rotated_sign_compress,
+    rotated_sign_compress_parameter,
+)
 from .quantized import (
     BroadcastDequantizer,
     BroadcastQuantizer,
@@ -112,6 +120,10 @@ __all__ = [
     "PersonalizedFedAVGAlgorithm",
     "QuantClientEndpoint",
     "RobustFedAVGAlgorithm",
+    "RotatedSignDelta",
+    "RotatedSignEndpoint",
+    "RotatedSignErrorFeedback",
+    "RotatedSignFedAVGAlgorithm",
     "SecAggEndpoint",
     "SecAggFedAVGAlgorithm",
     "SecAggSession",
@@ -136,6 +148,8 @@ __all__ = [
     "mx_compress_parameter",
     "normal_stream",
     "philox_uniforms",
+    "rotated_sign_compress",
+    "rotated_sign_compress_parameter",
     "secagg_mask_parameter",
     "sign_compress",
     "sign_compress_parameter",
@@ -341,6 +355,20 @@ def _register_builtin() -> None:
                 client_cls=None,  # type: ignore[arg-type]
                 server_cls=AggregationServer,
                 algorithm_cls=MXFedAVGAlgorithm,
+                **endpoint,
+            )
+    # FedAvg over randomly rotated 1-bit deltas, folded in the rotated domain, and the same with workers that
+    # compress their diffs before sending: the caller binds the session's seed through the endpoint's keyword
+    # arguments (endpoint_kwargs: {seed}), the same on every client
+    for name, endpoint in (("fed_avg_rsign", {}), ("fed_avg_rsign_ef", {"client_endpoint_cls": RotatedSignEndpoint})):
+        if not AlgorithmRepository.has_algorithm(name):
+            from .server import AggregationServer
+
+            AlgorithmRepository.register_algorithm(
+                algorithm_name=name,
+                client_cls=None,  # type: ignore[arg-type]
+                server_cls=AggregationServer,
+                algorithm_cls=RotatedSignFedAVGAlgorithm,
                 **endpoint,
             )
     # FedAvg under secure aggregation: the unmasking rule behind the masking endpoint. The session seed has no

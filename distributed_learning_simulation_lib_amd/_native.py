@@ -19,6 +19,7 @@ F32, F16, BF16, F64 = 0, 1, 2, 3
 QSGD_F32, QSGD_F64 = 4, 5  # quantised records (quantized.py)
 NNADQ_F32, NNADQ_F64 = 6, 7
 RECORD_CODES = (QSGD_F32, QSGD_F64, NNADQ_F32, NNADQ_F64)
+RSIGN_UNBIASED, RSIGN_MSE = 0, 1  # FEDAVG_RSIGN_*: the scale rules of fedavg_rsign_compress
 MXFP8, MXFP4 = 8, 9  # FEDAVG_MXFP8 / FEDAVG_MXFP4: the formats of fedavg_mx_compress and fedavg_mx_aggregate_delta
 # enum fedavg_status
 OK = 0
@@ -204,6 +205,13 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
                   c_void_p]),
     "fedavg_mx_aggregate_delta": (
         c_int32, [c_void_p, c_void_p, c_void_p, c_int32, _PD, c_int32, c_double, _PP, _PP, c_int32, c_void_p]),
+    # randomly rotated 1-bit compression with error feedback and its fold (rsign_kernels.hip); tables as raw addresses
+    "fedavg_rsign_compress": (
+        c_int32, [c_void_p, c_int32, c_int32, ctypes.c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fedavg_rsign_aggregate_delta": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_uint64, c_uint32, c_void_p, _PD, c_int32, c_double,
+                  _PP, _PP, c_int32, c_void_p]),
     "fedavg_check": (c_int32, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fedavg_find_nan_clients": (
         c_int32,

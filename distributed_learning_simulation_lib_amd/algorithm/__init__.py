@@ -14,6 +14,7 @@ from .lowrank_fed_avg_algorithm import LowRankFedAVGAlgorithm
 from .mx_fed_avg_algorithm import MXFedAVGAlgorithm
 from .personalized_aggregation_algorithm import PersonalizedFedAVGAlgorithm
 from .robust_aggregation_algorithm import RobustFedAVGAlgorithm
+from .rotated_sign_fed_avg_algorithm import RotatedSignFedAVGAlgorithm
 from .secagg_fed_avg_algorithm import SecAggFedAVGAlgorithm
 from .server_opt_algorithm import ServerOptFedAVGAlgorithm
 from .sign_fed_avg_algorithm import SignFedAVGAlgorithm
@@ -24,5 +25,5 @@ __all__ = ["AggregationAlgorithm", "BulyanFedAVGAlgorithm", "ClippedFedAVGAlgori
            "FLTrustFedAVGAlgorithm", "FedAVGAlgorithm", "FoolsGoldFedAVGAlgorithm", "GeometricMedianFedAVGAlgorithm", "GraphAlgorithm",
            "GraphNodeEmbeddingPassingAlgorithm", "GraphTopologyAlgorithm", "KrumFedAVGAlgorithm",
            "LowRankFedAVGAlgorithm", "MXFedAVGAlgorithm", "PersonalizedFedAVGAlgorithm",
-           "RobustFedAVGAlgorithm", "SecAggFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
+           "RobustFedAVGAlgorithm", "RotatedSignFedAVGAlgorithm", "SecAggFedAVGAlgorithm", "ServerOptFedAVGAlgorithm", "SignFedAVGAlgorithm", "SignMajorityVoteAlgorithm",
            "SparseFedAVGAlgorithm"]

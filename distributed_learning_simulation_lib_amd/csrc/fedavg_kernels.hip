@@ -3013,6 +3013,7 @@ const SideModule kSideModules[FEDAVG_MODULES] = {
     {fedavg_internal_secagg_constant, fedavg_internal_secagg_release},
     {fedavg_internal_lowrank_constant, fedavg_internal_lowrank_release},
     {fedavg_internal_mx_constant, fedavg_internal_mx_release},
+    {fedavg_internal_rsign_constant, fedavg_internal_rsign_release},
 };
 
 bool side_constant(const char* name, int64_t* v) {

@@ -28,6 +28,7 @@ enum fedavg_module {
   FEDAVG_MODULE_SECAGG,
   FEDAVG_MODULE_LOWRANK,
   FEDAVG_MODULE_MX,
+  FEDAVG_MODULE_RSIGN,
   FEDAVG_MODULES
 };
 
@@ -64,6 +65,7 @@ FEDAVG_INTERNAL int32_t fedavg_internal_gram_constant(const char* name, int64_t*
 FEDAVG_INTERNAL int32_t fedavg_internal_secagg_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL int32_t fedavg_internal_lowrank_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL int32_t fedavg_internal_mx_constant(const char* name, int64_t* out);
+FEDAVG_INTERNAL int32_t fedavg_internal_rsign_constant(const char* name, int64_t* out);
 FEDAVG_INTERNAL void fedavg_internal_robust_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_krum_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_point_release(int32_t device, void* state);
@@ -79,3 +81,4 @@ FEDAVG_INTERNAL void fedavg_internal_gram_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_secagg_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_lowrank_release(int32_t device, void* state);
 FEDAVG_INTERNAL void fedavg_internal_mx_release(int32_t device, void* state);
+FEDAVG_INTERNAL void fedavg_internal_rsign_release(int32_t device, void* state);

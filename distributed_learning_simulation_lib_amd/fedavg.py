@@ -40,6 +40,10 @@ from .rules import (  # noqa: F401 - re-exported: ``from ...fedavg import krum_s
 from .lowrank import LowRankDelta
 from .mx import FORMATS as MX_FORMATS
 from .mx import MXDelta, code_bytes
+from .rotated import MODES as RSIGN_MODES
+from .rotated import RotatedSignDelta
+from .rotated import geometry as rsign_geometry
+from .rotated import scale_dtype as rsign_scale_dtype
 from .sign import SignDelta, bit_bytes
 from .sparse import SparseDelta
 
@@ -480,6 +484,48 @@ class MXTable:
             raise ValueError(f"the mx deltas of one call share one format, not {sorted(formats)}")
         self.fmt = formats.pop() if formats else "mxfp8"
         self.dtype = torch.float64  # what the shared refusals ask of a table: no records
+        self.num_clients = n
+        self.layout = layout
+        self.device = device
+        self._keep = [list(row) for row in rows]
+
+
+class RotatedSignTable:
+    """Rows of rotated sign deltas as the C-ABI arrays of ``fedavg_rsign_aggregate_delta``:
+    ``rows[i][t]`` is client ``i``'s ``RotatedSignDelta`` of segment ``t`` of ``layout`` on ``device``,
+    all of one scale dtype, one seed and one draw, and of one tensor id per segment (built once,
+    reusable across calls; it keeps the tensors alive)."""
+
+    def __init__(self, rows: Sequence[Sequence[RotatedSignDelta]], layout: ModelLayout, device: torch.device) -> None:
+        n, T = len(rows), layout.num_segments
+        dtypes, streams = set(), set()
+        self.bptr = np.zeros(n * T, dtype=np.uint64)
+        self.sptr = np.zeros(n * T, dtype=np.uint64)
+        self.ids = np.zeros(T, dtype=np.uint32)
+        for i, row in enumerate(rows):
+            if len(row) != T:
+                raise ValueError(f"client {i}: one rotated sign delta per segment is required")
+            for t, (d, numel) in enumerate(zip(row, layout.numels)):
+                if not isinstance(d, RotatedSignDelta):
+                    raise TypeError(f"client {i}, tensor {t}: a RotatedSignDelta is required, not {type(d).__name__}")
+                if d.numel != numel or d.bits.device != device or d.scales.device != device \
+                        or not d.bits.is_contiguous() or not d.scales.is_contiguous():
+                    raise ValueError(f"client {i}, tensor {t}: a contiguous rotated sign delta of {numel} elements "
+                                     f"on {device} is required")
+                if d.tensor_id != rows[0][t].tensor_id:
+                    raise ValueError(f"client {i}, tensor {t}: tensor id {d.tensor_id}, client 0 has "
+                                     f"{rows[0][t].tensor_id}: the clients of a fold share the rotation")
+                dtypes.add(d.scales.dtype)
+                streams.add((d.seed, d.draw))
+                self.bptr[i * T + t] = d.bits.data_ptr()
+                self.sptr[i * T + t] = d.scales.data_ptr()
+                self.ids[t] = d.tensor_id
+        if len(streams) > 1:
+            raise ValueError(f"the clients of a fold share one (seed, draw), not {sorted(streams)}")
+        if len(dtypes) > 1:
+            raise ValueError(f"the rotated sign deltas of one call share one scale dtype, not {sorted(map(str, dtypes))}")
+        self.seed, self.draw = streams.pop() if streams else (0, 0)
+        self.dtype = dtypes.pop() if dtypes else torch.float32
         self.num_clients = n
         self.layout = layout
         self.device = device
@@ -1523,6 +1569,88 @@ class FedAvgContext:
             self._lib.fedavg_mx_aggregate_delta(
                 self._h, table.cptr.ctypes.data, table.sptr.ctypes.data, MX_FORMATS[table.fmt],
                 w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
+            )
+        )
+
+    def rsign_compress(self, deltas: Sequence[torch.Tensor], errors: Sequence[torch.Tensor | None] | None,
+                       bits: Sequence[torch.Tensor], scales: Sequence[torch.Tensor],
+                       residuals: Sequence[torch.Tensor], *, seed: int, draw: int,
+                       tensor_ids: Sequence[int] | None = None, mode: str = "unbiased") -> None:
+        """Randomly rotated 1-bit compression with error feedback of ``deltas`` (non-empty contiguous
+        tensors of one floating dtype on the context's device, of any sizes: the context's layout
+        plays no part) in one launch (``fedavg_rsign_compress``): with ``(B, nb, n_pad)
+        = rotated.geometry(numel)``, tensor ``t`` sends the signs of ``H_B (D (deltas[t] +
+        errors[t]))`` (``errors`` or an entry of it may be ``None``: no residual yet) as ``bits[t]``
+        (uint8, ``n_pad / 8`` bytes, 8-byte aligned) and one magnitude per block as ``scales[t]``
+        (``nb`` elements, fp64 for fp64 tensors and fp32 otherwise; ``mode`` "unbiased" or "mse"), and
+        leaves what it did not send in ``residuals[t]``, which may be ``errors[t]`` or ``deltas[t]``
+        itself. ``D`` is the Philox diagonal of ``seed``, ``draw`` and ``tensor_ids[t]`` (default:
+        the position). Asynchronous; a non-finite element latches the input flag (``flags()``)."""
+        T = len(deltas)
+        if mode not in RSIGN_MODES:
+            raise ValueError(f"the mode is one of {sorted(RSIGN_MODES)}, not {mode!r}")
+        if T == 0 or not (len(bits) == len(scales) == len(residuals) == T) or (
+                errors is not None and len(errors) != T):
+            raise ValueError("one bit, scale and residual tensor per delta and at least one delta are required")
+        ids = _stream_ids(seed, draw, tensor_ids, T)
+        dt = deltas[0].dtype
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"the rotated sign step takes fp32, fp16, bf16 or fp64 tensors, not {dt}")
+        ns = [x.numel() for x in deltas]
+        geo = [rsign_geometry(max(n, 1)) for n in ns]
+        nbytes, nb, sdt = [g[2] // 8 for g in geo], [g[1] for g in geo], rsign_scale_dtype(dt)
+        groups = (("error", errors or (), dt, ns), ("bit", bits, torch.uint8, nbytes), ("scale", scales, sdt, nb),
+                  ("residual", residuals, dt, ns))
+        t, fault = _first(T, self._first_unfit(deltas, dt), next((t for t, n in enumerate(ns) if n == 0), T),
+                          *[self._first_unfit(g, dty, sizes) if g else T for _, g, dty, sizes in groups])
+        if fault == 0:
+            raise self._flat_refusal("delta", t, dt)
+        if fault == 1:
+            raise ValueError(f"delta {t}: an empty tensor has no block, and is the caller's")
+        if fault >= 2:
+            what, _, dty, sizes = groups[fault - 2]
+            raise self._flat_refusal(what, t, dty, sizes[t])
+        xptr, bptr, sptr, rptr = (_addresses(deltas, ns), _addresses(bits, nbytes), _addresses(scales, nb),
+                                  _addresses(residuals, ns))
+        eptr = None if errors is None else _addresses(errors, ns)
+        ns = np.array(ns, dtype=np.int64)
+        _native.check(
+            self._lib.fedavg_rsign_compress(
+                self._h, DTYPE_CODES[dt], RSIGN_MODES[mode], int(seed), int(draw), ids.ctypes.data, xptr.ctypes.data,
+                None if eptr is None else eptr.ctypes.data, ns.ctypes.data, T, bptr.ctypes.data, sptr.ctypes.data,
+                rptr.ctypes.data, self.stream,
+            )
+        )
+
+    def rsign_aggregate_delta(self, rows: Sequence[Sequence[RotatedSignDelta]] | RotatedSignTable,
+                              weights: Sequence[float], divisor: float, base: Sequence[torch.Tensor],
+                              outs: Sequence[torch.Tensor], out_dtype: torch.dtype = torch.float64) -> None:
+        """The fold of rotated sign deltas against ``base`` in one launch
+        (``fedavg_rsign_aggregate_delta``): per block ``m = (sum_i d_i * w_i) /
+        divisor`` with ``d_i`` ``-s_i`` where client ``i``'s bit is set and ``+s_i`` elsewhere, then
+        ``outs[t] = base[t] + D H_B m``: the average is taken in the rotated domain and the rotation
+        inverted once, so this is not the bit pattern of ``aggregate_delta`` on the densified deltas.
+        ``rows[i][t]`` is client ``i``'s ``RotatedSignDelta`` of segment ``t`` on the context's device,
+        all of one scale dtype, seed and draw and of one tensor id per segment (or a
+        ``RotatedSignTable`` built from such rows once). ``base`` is one contiguous fp64 tensor per
+        segment, ``outs`` one contiguous ``out_dtype`` tensor per segment, none of them its base's own
+        storage. The accumulator is not touched; the NaN flags are the caller's to read
+        (``raise_on_nan``). Refused before any launch: no clients, more than 1024, a delta that does
+        not match its segment, mixed scale dtypes or rotations, a non-finite weight, a divisor that
+        is not finite and > 0, a base or an output that does not match, an output that is its base."""
+        ocode = out_code(out_dtype)
+        table = rows if isinstance(rows, RotatedSignTable) else RotatedSignTable(rows, self.layout, self.device)
+        if table.layout != self.layout or table.device != self.device:
+            raise ValueError("the rotated sign table was built for another layout or device")
+        self._refuse_before_table(table, table.dtype, "the rotated sign fold", "s", _native.POINT_MAX_CLIENTS)
+        n = table.num_clients
+        w = _client_scalars(weights, n, "weight")
+        divisor = _divisor(divisor)
+        zp, op = self._source_and_outputs("base", base, outs, out_dtype, "the rotated sign fold is not in-place")
+        _native.check(
+            self._lib.fedavg_rsign_aggregate_delta(
+                self._h, table.bptr.ctypes.data, table.sptr.ctypes.data, dtype_code(table.dtype), table.seed, table.draw,
+                table.ids.ctypes.data, w.ctypes.data_as(_DBL), n, divisor, zp, op, ocode, self.stream,
             )
         )
 

@@ -40,6 +40,8 @@ from ..lowrank import densify_parameter as densify_lowrank_parameter
 from ..lowrank import is_lowrank
 from ..mx import densify_parameter as densify_mx_parameter
 from ..mx import is_mx
+from ..rotated import densify_parameter as densify_rotated_parameter
+from ..rotated import is_rotated
 from ..sign import densify_parameter as densify_sign_parameter
 from ..sign import is_sign
 from ..sparse import densify_parameter, is_sparse
@@ -216,6 +218,11 @@ class AggregationServer:
         if is_delta_message(data) and is_mx(data.delta_parameter):
             if not getattr(self._algorithm, "accepts_mx_messages", False):
                 data.delta_parameter = densify_mx_parameter(data.delta_parameter)
+        # and for ``rotated.RotatedSignDelta`` values (rotated 1-bit signs) and ``accepts_rotated_messages``
+        # (RotatedSignFedAVGAlgorithm folds the bits in the rotated domain)
+        if is_delta_message(data) and is_rotated(data.delta_parameter):
+            if not getattr(self._algorithm, "accepts_rotated_messages", False):
+                data.delta_parameter = densify_rotated_parameter(data.delta_parameter)
         # ``secagg.MaskedDelta`` values cannot be densified: one client's words are noise, and only
         # an algorithm with ``accepts_masked_messages`` (SecAggFedAVGAlgorithm) can remove the masks
         if is_delta_message(data) and is_masked(data.delta_parameter):

@@ -179,7 +179,11 @@ int32_t fedavg_build_flags(void);
  * "mx_block" (32: elements that share a scale byte), "mx_tile" (elements per workgroup of
  * fedavg_mx_compress and fedavg_mx_aggregate_delta), "mx_threads" (lanes of an encoder workgroup and
  * of an FP8 fold workgroup; an FP4 fold workgroup has half of them), "mx_batch" (clients whose scale
- * bytes the fold stages at a time) and "mx_max_clients": none of them enters the result.
+ * bytes the fold stages at a time) and "mx_max_clients": none of them enters the result;
+ * "rsign_tile" (4096: padded elements per workgroup of fedavg_rsign_compress and
+ * fedavg_rsign_aggregate_delta, and the largest block), "rsign_min_block" (64: the smallest block),
+ * "rsign_threads", "rsign_batch" (clients whose words and scales the fold stages at a time) and
+ * "rsign_max_clients": the two block bounds are the format's, the others do not enter the result.
  * FEDAVG_ERR_INVALID for an unknown name. */
 int32_t fedavg_kernel_constant(const char* name, int64_t* out);
 
@@ -1263,6 +1267,74 @@ int32_t fedavg_mx_aggregate_delta(fedavg_ctx* ctx, const void* const* code_ptrs 
                                   const double* weights /* [n], host */, int32_t num_clients, double divisor,
                                   const double* const* base_ptrs /* [T], device fp64 */,
                                   void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
+
+/*
+ * Randomly rotated 1-bit client updates (DRIVE: Vargaftik et al., NeurIPS 2021; the random rotation of
+ * Suresh et al., ICML 2017): one bit per coordinate, the sign of the diff after a randomised
+ * Walsh-Hadamard rotation, and one magnitude per block.
+ * Format of a tensor of n >= 1 elements: block size B = min(4096, max(64, next_pow2(n))), nb = ceil(n / B)
+ * blocks, n_pad = nb * B. `bits`: n_pad / 8 bytes, 8-byte aligned, element e is bit e % 64 of the 64-bit
+ * word e / 64. `scales`: nb elements, fp32 for fp32 / fp16 / bf16 tensors and fp64 for fp64 tensors.
+ * The diagonal: D[e] = -1 where bit e % 32 of word (e % 128) / 32 of the Philox4x32-10 block e / 128 is
+ * set, +1 elsewhere; the block's key is (seed & 0xffffffff, seed >> 32), its counter (block & 0xffffffff,
+ * block >> 32, tensor_ids[t], draw), as in fedavg_quant_encode.
+ * The transform H_B acts on each block on its own and is unnormalised: for h = 1, 2, 4, ..., B / 2 in
+ * that order, every pair (i, i + h) with i & h == 0 becomes (a + b, a - b), each one separately rounded
+ * fp64 operation. sum_tree(x) is the fp64 sum of a block by the adjacent-pair tree in index order (one
+ * level is x[2 i] + x[2 i + 1]).
+ *
+ * fedavg_rsign_compress, the client step over num_tensors device tensors of one dtype (FEDAVG_F32 / F16
+ * / BF16 / F64), tensor t of numels[t] (host, 1 .. 2^31 - 1) elements, with error feedback, in one
+ * launch whatever num_tensors is. Per tensor:
+ *   total[e] = delta[e] + error[e], rounded once to nearest even into the dtype; without an error
+ *              total[e] is delta[e] bit for bit;
+ *   u[e]     = D[e] * total[e] (exact, in fp64) for e < n, +0.0 for n <= e < n_pad;   y = H_B u;
+ *   per block: l1 = sum_tree(|y|), l2 = sum_tree(y * y) (the product rounded first);
+ *              sigma = l2 / l1 (FEDAVG_RSIGN_UNBIASED: DRIVE's |x|^2 / |Rx|_1) or l1 / B (FEDAVG_RSIGN_MSE);
+ *              s = sigma / B, +0.0 where l1 == 0;  scale = s rounded to nearest even into the scale dtype;
+ *   bit[e]   = the sign bit of y[e], for every e < n_pad;
+ *   z = H_B v with v[e] = -scale where bit[e] is set, +scale elsewhere (widened exactly);
+ *   sent[e]  = D[e] * z[e], rounded once into the dtype;
+ *   residual_ptrs[t][e] = total[e] - sent[e], rounded once to nearest even into the dtype, for e < n.
+ * residual_ptrs[t] may be error_ptrs[t] or delta_ptrs[t] (every element is read and then written by the
+ * same lane); no other overlap is allowed. No atomics, no host round trip: asynchronous on `stream`. A
+ * non-finite total[e] latches FEDAVG_FLAG_INPUT_NAN (the outputs are then unspecified but stay inside
+ * their buffers). The accumulator and its state are not touched. Refused before any launch:
+ * FEDAVG_ERR_INVALID (a bad dtype or mode; a NULL table other than error_ptrs; num_tensors < 1 or > 2^20;
+ * numels[t] < 1 or > 2^31 - 1; a NULL delta, residual, bit or scale buffer; a buffer not aligned to its
+ * element; a bit buffer not 8-byte aligned), FEDAVG_ERR_STATE (an open dynamic wave).
+ *
+ * fedavg_rsign_aggregate_delta, the fold of such payloads against the fp64 base in one launch. All
+ * clients share seed, draw and tensor_ids (one id per segment of the context's layout); scale_dtype is
+ * FEDAVG_F32 or FEDAVG_F64. Per padded element e of segment t, with client i's payload bit_ptrs[i * T +
+ * t], scale_ptrs[i * T + t]:
+ *   d_i = -s_i where client i's bit is set, +s_i elsewhere (s_i its scale of e's block, widened exactly);
+ *   p_i = d_i * w_i;   acc = p_0, then acc = acc + p_i in table order;   m = acc / divisor;
+ *   z = H_B m;   out[e] = base[e] + D[e] * z[e] for e < n
+ * each a separately rounded fp64 operation (fp32 out: that result rounded to nearest even). The average
+ * is taken before the inverse rotation, so this is NOT the bit pattern of fedavg_aggregate_delta on the
+ * densified deltas: the contract is its own. FEDAVG_FLAG_INPUT_NAN for a NaN d_i, FEDAVG_FLAG_ACC_NAN
+ * for a NaN acc, FEDAVG_FLAG_RESULT_NAN for a NaN out[e]. The accumulator is not touched. No atomics.
+ * Asynchronous on `stream`. Refused before any launch: FEDAVG_ERR_INVALID (a bad scale_dtype or
+ * out_dtype, NULL tables or entries, num_clients < 1 or > FEDAVG_POINT_MAX_CLIENTS, a non-finite weight,
+ * a divisor that is not finite and > 0, a misaligned bit buffer, scale buffer, base or output, out ==
+ * base), FEDAVG_ERR_STATE (an open dynamic wave).
+ */
+#define FEDAVG_RSIGN_UNBIASED 0
+#define FEDAVG_RSIGN_MSE 1
+int32_t fedavg_rsign_compress(fedavg_ctx* ctx, int32_t dtype, int32_t mode, uint64_t seed, uint32_t draw,
+                              const uint32_t* tensor_ids /* [T], host */,
+                              const void* const* delta_ptrs /* [T], device */,
+                              const void* const* error_ptrs /* [T], device, or NULL; entries may be NULL */,
+                              const int64_t* numels /* [T], host */, int32_t num_tensors,
+                              void* const* bit_ptrs /* [T], device */, void* const* scale_ptrs /* [T], device */,
+                              void* const* residual_ptrs /* [T], device */, void* stream);
+int32_t fedavg_rsign_aggregate_delta(fedavg_ctx* ctx, const void* const* bit_ptrs /* [n][T], device */,
+                                     const void* const* scale_ptrs /* [n][T], device */, int32_t scale_dtype,
+                                     uint64_t seed, uint32_t draw, const uint32_t* tensor_ids /* [T], host */,
+                                     const double* weights /* [n], host */, int32_t num_clients, double divisor,
+                                     const double* const* base_ptrs /* [T], device fp64 */,
+                                     void* const* out_ptrs /* [T], device */, int32_t out_dtype, void* stream);
 
 /*
  * Synchronise `stream` and report the NaN flag: FEDAVG_OK, FEDAVG_ERR_NAN_INPUT (robust rules),
